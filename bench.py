@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- 480-sample frames/sec of the batched process_frame path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 may be started either way: under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the
 environment, what the driver does) or as a plain `python bench.py --gpus N`, in which case this script re-executes itself
@@ -23,7 +23,9 @@ frames (default 48 = 0.48 s of audio per stream per call).  Workloads are BASELI
 Synthetic 48 kHz sine + noise per stream, inputs resident in HBM before the timed region.  Streams are
 independent, so ranks shard them with no data-path collective (weak scaling); the only collective aggregates the result.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps of the
+headline workload and prints the line; everything else it can measure runs only with --full, which adds these objects:
+  tick          the same workload at one frame per call (the default batch, and a batch sized for ticks)
   roofline      dominant kernel: algorithmic bytes per launch / its average duration measured live with HIP events on
                 the launch stream (a second, event-instrumented pass over the same workload)
   cpu_baseline  the CPU oracle (scalar C port of the reference, f32 FFT) on the host's cores: the synthetic mix at
@@ -32,7 +34,14 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
                 reference cannot be built here (no cargo), hence kind "port".
   also          (default N=1 run only) the same measurement on configs[1] and configs[4], so the driver's line carries them
                 (each timed for at least 0.5 s)
+  default_semantics  (default N=1 run only) the headline workload under the library's default call ordering
   host_boundary (default N=1 run only) the headline workload through the host-buffer entry point: PCIe-inclusive, never `value`
+The --no-* options leave out single parts of a --full run.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step, as a caller receives it, before anything else
+touches the buffers: DIR/out.npy (float32 [streams, frames, 480], the denoised audio) and DIR/vad.npy (float32 [streams, frames])
+of a fixed sample of rank 0's streams (the same streams for the same arguments; at most 64 MB in all).  The inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -206,11 +215,16 @@ def parse_args(argv=None):
     ap.add_argument("--layout", choices=["stream-major", "frame-major"], default="stream-major",
                     help="resident buffers as [stream][frame][480] (one stream's audio contiguous, the reference's per-stream slices side by "
                          "side) or [frame][stream][480] (the batch's frames interleaved); f32 mono only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-host", action="store_true", help="skip the PCIe-inclusive host-buffer measurement of the default run")
-    ap.add_argument("--no-tick", action="store_true", help="skip the one-frame-per-call measurement")
-    ap.add_argument("--no-also", action="store_true", help="skip the extra configs[1] / configs[4] measurements of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (tick, roofline pass, configs[1] / configs[4], default call "
+                         "ordering, host boundary, CPU baseline); a plain run times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (a fixed sample of streams) to DIR/out.npy and DIR/vad.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the event-instrumented roofline pass")
+    ap.add_argument("--no-host", action="store_true", help="with --full: skip the PCIe-inclusive host-buffer measurement of the default run")
+    ap.add_argument("--no-tick", action="store_true", help="with --full: skip the one-frame-per-call measurement")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the extra configs[1] / configs[4] measurements of the default run")
     ap.add_argument("--min-timed-s", type=float, default=0.5, help="the `also` entries run enough steps to be timed for at least this long")
     ap.add_argument("--pool-bytes", type=float, default=6.5e9, help="HBM budget for the resident input pool (and as much again for the output)")
     ap.add_argument("--single-process", action="store_true",
@@ -219,7 +233,10 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing check without a GPU: gloo backend, CPU tensors, the library named by NNN_LIBRARY (the tests "
                          "point it at the SIMT-interpreter build), a few streams; the numbers mean nothing")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dump_outputs and (args.config == 0 or args.single_process or args.workload != "denoise"):
+        ap.error("--dump-outputs: the denoise workload of configs 1-4 under one process per GPU only")
+    return args
 
 
 def pmc_profile(kind, S):
@@ -263,10 +280,35 @@ def isa_arithmetic():
     return out, "profiles/" + os.path.basename(paths[-1])
 
 
-def measure(args, S, model_path, rank, world, dev, local_rank, dist, torch, want_tick=True, want_roofline=True, min_timed_s=0.0):
+DUMP_BYTES = 64 << 20   # --dump-outputs: the most it writes
+
+
+def dump_outputs(path, torch, y, vad, S, pool, layout, channels, positions):
+    """--dump-outputs: the outputs at the absolute frame positions `positions` (the last timed step) of a fixed, seeded sample of
+    streams, as float32 out.npy [streams, frames, 480] and vad.npy [streams, frames].  `layout`: "stream" ([S, pool, 480]), "frame"
+    ([pool, S, 480]) or "packed" ([S // channels, pool * 480, channels]) -- the resident buffers of measure()."""
+    import numpy as np
+    positions = positions[-min(pool, DUMP_BYTES // (481 * 4)):]   # a step longer than the pool has overwritten its own first frames
+    n = max(1, min(S, 256, DUMP_BYTES // (len(positions) * 481 * 4)))
+    streams = torch.as_tensor(np.sort(np.random.default_rng(0).choice(S, n, replace=False)), device=y.device)
+    frames = torch.as_tensor([p % pool for p in positions], device=y.device)
+    if layout == "frame":
+        out = y[:, streams][frames].transpose(0, 1)
+    elif layout == "packed":
+        out = y.reshape(S // channels, pool, 480, channels)[streams // channels, :, :, streams % channels][:, frames]
+    else:
+        out = y[streams][:, frames]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "out.npy"), out.float().cpu().numpy())
+    np.save(os.path.join(path, "vad.npy"), vad[:, streams][frames].t().float().cpu().numpy())
+
+
+def measure(args, S, model_path, rank, world, dev, local_rank, dist, torch, want_tick=True, want_roofline=True, min_timed_s=0.0,
+            dump_dir=None):
     """One workload on this rank's device.  Returns (dict of measured quantities aggregated over ranks, roofline pass): the
     second is a callable (or None) that runs the event-instrumented pass on this rank and returns the extra fields -- rank 0
-    calls it after the ranks have parted, so that nobody idles behind it."""
+    calls it after the ranks have parted, so that nobody idles behind it.  `dump_dir`: rank 0 writes the last timed step's
+    outputs there (dump_outputs) before anything else runs on the buffers."""
     import nnnoiseless_amd as nn
     from nnnoiseless_amd.shard import aggregate, gather
     from nnnoiseless_amd.synthetic import make_streams_device
@@ -354,6 +396,9 @@ def measure(args, S, model_path, rank, world, dev, local_rank, dist, torch, want
     elapsed = time.perf_counter() - t0
     if bd.fault():                            # (a caller that synchronises its own stream has to ask: nnn_batch_fault)
         raise SystemExit("bench: the library reports a frame hand-off fault (nnn_batch_fault): results invalid")
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, torch, y, vad, S, pool, "packed" if fmt or Cc > 1 else ("frame" if fm else "stream"), Cc,
+                     list(range((W + K - 1) * fps, (W + K) * fps)))
     d = dist if world > 1 else None
     frames_done, elapsed_max = aggregate(d, S * fps * K, elapsed, dev)
     per_rank = [round(v) for v in gather(d, S * fps * K / max(local, 1e-9), dev)]   # frames/s of every rank on its own clock
@@ -756,7 +801,8 @@ def main():
         args.frames_per_step = min(args.frames_per_step, 3)
         args.steps, args.warmup = min(args.steps, 2), min(args.warmup, 1)
     model_path = args.model or cfg["model"]
-    res, roof = measure(args, S, model_path, rank, world, dev, local_rank, dist, torch, want_tick=not args.no_tick, want_roofline=not args.no_roofline)
+    res, roof = measure(args, S, model_path, rank, world, dev, local_rank, dist, torch, want_tick=args.full and not args.no_tick,
+                        want_roofline=args.full and not args.no_roofline, dump_dir=args.dump_outputs)
     # Every collective of the run is behind us (the aggregation inside measure): the ranks part here, and what only rank 0
     # reports -- the event-instrumented pass, the other configurations, the host-buffer rates, the CPU baseline -- runs with no
     # other rank waiting behind a barrier for it.
@@ -768,7 +814,7 @@ def main():
     if roof:
         res.update(roof())
 
-    default_run = (args.config == 2 and args.streams is None and args.model is None and world == 1 and args.pcm == "f32"
+    default_run = (args.full and args.config == 2 and args.streams is None and args.model is None and world == 1 and args.pcm == "f32"
                    and args.channels == 1 and not args.dry_run)
     also = None
     if default_run and not args.no_also:
@@ -807,7 +853,7 @@ def main():
         host = host_boundary(args.frames_per_step)
 
     cpu = None
-    if not args.no_cpu_baseline and not args.dry_run:
+    if args.full and not args.no_cpu_baseline and not args.dry_run:
         cpu = cpu_baseline()
 
     fps = args.frames_per_step

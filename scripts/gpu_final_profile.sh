@@ -5,14 +5,15 @@
 set -u
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
-mkdir -p gpurun_out; rm -rf gpurun_out/prof
-timeout 900 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err; echo "bench rc=$?"; cut -c1-260 gpurun_out/bench.json
+OUT=${OUT:-$R/out}
+mkdir -p $OUT; rm -rf $OUT/prof
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-260 $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats -d "$R/gpurun_out/prof" -- python "$R/bench.py" --steps 10 --warmup 2 --no-cpu-baseline --no-also > "$R/gpurun_out/prof.log" 2>&1; echo "rocprof rc=$?"
+timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -- python "$R/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline --no-also > "$OUT/prof.log" 2>&1; echo "rocprof rc=$?"
 cd "$R"
-DB=$(find gpurun_out/prof -name '*_results.db' | head -1)
-python scripts/rocpd_kernel_stats.py "$DB" > gpurun_out/kernel_stats.md; head -10 gpurun_out/kernel_stats.md
-find gpurun_out/prof -name '*.db' -delete
+DB=$(find $OUT/prof -name '*_results.db' | head -1)
+python scripts/rocpd_kernel_stats.py "$DB" > $OUT/kernel_stats.md; head -10 $OUT/kernel_stats.md
+find $OUT/prof -name '*.db' -delete
 bash scripts/gpu_pmc_traffic.sh 2>&1 | tail -10
 bash scripts/gpu_trace.sh 2>&1 | head -8
 bash scripts/gpu_scale_profile.sh 2>&1 | tail -11

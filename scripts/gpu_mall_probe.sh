@@ -10,7 +10,7 @@ O=$R/gpurun_out; mkdir -p $O
 for S in 8192; do
   for F in 2 4 8 24; do
     ST=$((960 / F))
-    timeout 300 python bench.py --streams $S --frames-per-step $F --steps $ST --warmup 4 --no-cpu-baseline --no-also --no-tick --no-host > $O/mall.json 2> $O/mall.err
+    timeout 300 python bench.py --full --streams $S --frames-per-step $F --steps $ST --warmup 4 --no-cpu-baseline --no-also --no-tick --no-host > $O/mall.json 2> $O/mall.err
     python - <<PY
 import json
 try:

@@ -17,7 +17,7 @@ tests)
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
   ;;
 bench)
-  timeout 900 python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; echo "bench rc=$?"; cut -c1-300 $O/${TAG}_bench_default.json
+  timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; echo "bench rc=$?"; cut -c1-300 $O/${TAG}_bench_default.json
   python - <<PY
 import json
 try:
@@ -40,7 +40,7 @@ ab)
     if [ "$V" = default ]; then unset NNN_LIBRARY; else export NNN_LIBRARY=$R/nnnoiseless_amd/lib/variants/$V.so; fi
     for C in ${CONFIGS:-2 1}; do
       ST=12; [ "$C" = 1 ] && ST=120
-      timeout 300 python bench.py --config $C --steps $ST --warmup 3 --no-cpu-baseline --no-also --no-tick --no-host > $O/ab.json 2>$O/ab.err
+      timeout 300 python bench.py --full --config $C --steps $ST --warmup 3 --no-cpu-baseline --no-also --no-tick --no-host > $O/ab.json 2>$O/ab.err
       python - <<PY
 import json
 try:
@@ -58,7 +58,7 @@ stats)
     ST=10; [ "$C" = 1 ] && ST=40
     rm -rf $O/prof_c$C $O/prof_seq_c$C
     timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_c$C -- python $R/bench.py --config $C --steps $ST --warmup 2 --no-cpu-baseline --no-also --no-tick --no-host --no-roofline > $O/prof_c$C.log 2>&1; echo "rocprof config $C rc=$?"
-    NNN_SCHED=seq timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_seq_c$C -- python $R/bench.py --config $C --steps $ST --warmup 2 --no-cpu-baseline --no-also --no-tick --no-host > $O/prof_seq_c$C.log 2>&1; echo "rocprof seq config $C rc=$?"
+    NNN_SCHED=seq timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_seq_c$C -- python $R/bench.py --full --config $C --steps $ST --warmup 2 --no-cpu-baseline --no-also --no-tick --no-host > $O/prof_seq_c$C.log 2>&1; echo "rocprof seq config $C rc=$?"
     for K in prof_c$C prof_seq_c$C; do
       DB=$(find $O/$K -name '*_results.db' | head -1)
       python $R/scripts/rocpd_kernel_stats.py "$DB" > $O/${TAG}_kernel_stats_${K#prof_}.md; head -9 $O/${TAG}_kernel_stats_${K#prof_}.md

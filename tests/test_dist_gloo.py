@@ -138,3 +138,21 @@ def test_bench_pool_wrap_stays_in_bounds():
                                  "--pool-bytes", str(3 * 480 * 4 * 2)])          # room for 2 frames: every step wraps
     assert rc == 0, err[-2000:]
     assert lines[0]["pool_frames"] == 2 and lines[0]["outputs_finite"]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float32 arrays: the same values from run to run (seeded inputs), and
+    the same streams' values whatever layout the resident buffers have."""
+    import numpy as np
+    dumps = {}
+    for tag, extra in (("a", []), ("b", []), ("frame", ["--layout", "frame-major"]), ("ch2", ["--channels", "2"])):
+        rc, lines, err = _run_bench(["--dump-outputs", str(tmp_path / tag)] + extra)
+        assert rc == 0, err[-2000:]
+        dumps[tag] = {n: np.load(tmp_path / tag / f"{n}.npy") for n in ("out", "vad")}
+    S, F = lines[0]["config"]["streams_per_gpu"], lines[0]["config"]["frames_per_step"]
+    assert dumps["a"]["out"].dtype == np.float32 and dumps["a"]["out"].shape == (S, F, 480)
+    assert dumps["a"]["vad"].dtype == np.float32 and dumps["a"]["vad"].shape == (S, F)
+    assert np.isfinite(dumps["a"]["out"]).all() and np.abs(dumps["a"]["out"]).max() > 0
+    for tag in ("b", "frame", "ch2"):
+        for n in ("out", "vad"):
+            assert np.array_equal(dumps["a"][n], dumps[tag][n]), (tag, n)
