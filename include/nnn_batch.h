@@ -89,6 +89,50 @@ int nnn_batch_save_state(nnn_batch *b, void *host_dst, size_t dst_bytes);
 int nnn_batch_load_state(nnn_batch *b, const void *host_src, size_t src_bytes);
 
 /*
+ * Per-stream state records: ONE stream's DenoiseState (src/denoise.rs:37-42) in the reference's own terms, independent of the batch
+ * it came from (no ring slots, tiles, frame counts or group sizes): a record exported from any slot of any batch imports into any
+ * slot of any other batch -- another max_group_frames, stream count, frame count, device, or a lone DenoiseState -- whose stream
+ * runs a model of the same GRU sizes, and both continue bit-identically.  Fixed size, 16-byte multiple, little-endian, 32-bit words
+ * (f32 unless marked).  Byte offsets:
+ */
+#define NNN_STREAM_STATE_BYTES 11232
+#define NNN_STREAM_STATE_VERSION 1
+#define NNN_STREAM_STATE_MAGIC 0x3153534Eu        /* "NSS1" */
+#define NNN_STREAM_STATE_OFF_MAGIC 0              /* u32 NNN_STREAM_STATE_MAGIC                                                   */
+#define NNN_STREAM_STATE_OFF_VERSION 4            /* u32 NNN_STREAM_STATE_VERSION                                                 */
+#define NNN_STREAM_STATE_OFF_SIZE 8               /* u32 NNN_STREAM_STATE_BYTES                                                   */
+#define NNN_STREAM_STATE_OFF_GRU_SIZES 12         /* i32 [3] vad / noise / denoise GRU neurons of the model (src/rnn.rs:65-70)    */
+#define NNN_STREAM_STATE_OFF_MEM_ID 24            /* i32 cepstral ring position (src/features.rs:26)                             */
+#define NNN_STREAM_STATE_OFF_LAST_PERIOD 28       /* i32 PitchFinder::last_period (src/pitch.rs:5)                               */
+#define NNN_STREAM_STATE_OFF_LAST_GAIN 32         /* f32 PitchFinder::last_gain                                                  */
+#define NNN_STREAM_STATE_OFF_MEM_HP_X 36          /* f32 [2] high-pass biquad state (src/features.rs:27)                         */
+                                                  /* 44 .. 63 reserved, zero                                                      */
+#define NNN_STREAM_STATE_OFF_INPUT_MEM 64         /* f32 [1728] high-passed input history, oldest first (src/features.rs:97-104)  */
+#define NNN_STREAM_STATE_OFF_SYNTHESIS_MEM 6976   /* f32 [480] overlap memory (src/features.rs:263-275)                          */
+#define NNN_STREAM_STATE_OFF_CEPSTRAL_MEM 8896    /* f32 [8][22] cepstral history, [ring slot][band] (src/features.rs:167-194)   */
+#define NNN_STREAM_STATE_OFF_LASTG 9600           /* f32 [22] last applied gains (src/denoise.rs:106-109), then 2 zero words     */
+#define NNN_STREAM_STATE_OFF_VAD_GRU 9696         /* f32 [128] the first nv used, the rest zero (src/rnn.rs:330-341)             */
+#define NNN_STREAM_STATE_OFF_NOISE_GRU 10208      /* f32 [128] the first nn used                                                  */
+#define NNN_STREAM_STATE_OFF_DENOISE_GRU 10720    /* f32 [128] the first ndn used                                                 */
+/*
+ * streams[i] (host memory) names the stream of record i.  Work is enqueued in call order with the processing calls -- after every call
+ * made before, before every call made after, pipelined calls under nnn_batch_set_inputs_ready included -- on the batch's own stream
+ * (host variants; they wait for it) or on hip_stream (device variants, NULL = the batch's own stream; they return once the work is
+ * enqueued).  Every call checks everything it can before it writes anything and refuses, changing nothing, on: an index outside
+ * [0, n_streams); a repeated index (import, reset); a record whose magic, version, size or GRU sizes do not match the target stream's
+ * model (activations may differ: they are not state); a NULL pointer or a short buffer; an export from a batch whose nnn_batch_fault is
+ * set.  Reset and import leave that sticky fault as it is.  The device import checks the records on the device: a list with a bad record
+ * is dropped whole (nothing written) and the refusal is reported by the next nnn_batch_synchronize.
+ */
+/* streams back to freshly-created state (DenoiseState::new, src/features.rs:58-74): the import of an all-zero record */
+int nnn_batch_reset_streams(nnn_batch *b, const int *streams, int n);
+int nnn_batch_export_streams(nnn_batch *b, const int *streams, int n, void *host_dst, size_t dst_bytes);
+int nnn_batch_import_streams(nnn_batch *b, const int *streams, int n, const void *host_src, size_t src_bytes);
+/* records in device memory of the batch's device: n * NNN_STREAM_STATE_BYTES bytes at d_dst / d_src, 4-byte aligned */
+int nnn_batch_export_streams_device(nnn_batch *b, const int *streams, int n, void *d_dst, void *hip_stream);
+int nnn_batch_import_streams_device(nnn_batch *b, const int *streams, int n, const void *d_src, void *hip_stream);
+
+/*
  * n_frames x process_frame for every stream, buffers resident in device memory.
  *   sample i of frame t of stream s:  d_in [s * stream_stride + t * frame_stride + i]   (floats)
  *                                     d_out[s * stream_stride + t * frame_stride + i]   (may alias d_in)

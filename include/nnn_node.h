@@ -69,6 +69,12 @@ int nnn_node_process_device(nnn_node *n, const float *const *d_in, float *const 
 int nnn_node_process_device_streams(nnn_node *n, const float *const *d_in, float *const *d_out, float *const *d_vad,
                                     void *const *hip_streams, int n_tables, int n_frames, size_t stream_stride, size_t frame_stride);
 int nnn_node_synchronize(nnn_node *n);
+/* Per-stream state records (nnn_batch.h, NNN_STREAM_STATE_BYTES each) by NODE-global stream index: every index is routed to the shard
+ * that holds it, record i belonging to streams[i] wherever it lives.  The whole list is checked on every shard before any shard is
+ * written; the shards' parts then run one after the other on the caller's thread, each waiting for its device. */
+int nnn_node_reset_streams(nnn_node *n, const int *streams, int n_list);
+int nnn_node_export_streams(nnn_node *n, const int *streams, int n_list, void *host_dst, size_t dst_bytes);
+int nnn_node_import_streams(nnn_node *n, const int *streams, int n_list, const void *host_src, size_t src_bytes);
 /* 1 if any shard reports nnn_batch_fault */
 int nnn_node_fault(const nnn_node *n);
 

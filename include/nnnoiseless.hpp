@@ -159,6 +159,27 @@ class BatchDenoiser {
         return buf;
     }
     void load_state(const std::vector<uint8_t> &buf) { check(nnn_batch_load_state(b_.get(), buf.data(), buf.size())); }
+    // per-stream state records (NNN_STREAM_STATE_BYTES each, record i for streams[i]): portable between slots, batches and DenoiseStates
+    void reset_streams(const std::vector<int> &streams) { check(nnn_batch_reset_streams(b_.get(), streams.data(), (int)streams.size())); }
+    std::vector<uint8_t> export_streams(const std::vector<int> &streams) const
+    {
+        std::vector<uint8_t> buf(streams.size() * NNN_STREAM_STATE_BYTES);
+        check(nnn_batch_export_streams(b_.get(), streams.data(), (int)streams.size(), buf.data(), buf.size()));
+        return buf;
+    }
+    void import_streams(const std::vector<int> &streams, const std::vector<uint8_t> &records)
+    {
+        check(nnn_batch_import_streams(b_.get(), streams.data(), (int)streams.size(), records.data(), records.size()));
+    }
+    // records in device memory, asynchronous on hip_stream (nullptr: the batch's own stream)
+    void export_streams_device(const std::vector<int> &streams, void *d_dst, void *hip_stream = nullptr)
+    {
+        check(nnn_batch_export_streams_device(b_.get(), streams.data(), (int)streams.size(), d_dst, hip_stream));
+    }
+    void import_streams_device(const std::vector<int> &streams, const void *d_src, void *hip_stream = nullptr)
+    {
+        check(nnn_batch_import_streams_device(b_.get(), streams.data(), (int)streams.size(), d_src, hip_stream));
+    }
     nnn_batch *raw() { return b_.get(); }
 
   private:
@@ -205,6 +226,14 @@ class DenoiseState {
         return vad;
     }
     DenoiseState clone() const { return DenoiseState(b_.clone()); }   // #[derive(Clone)], src/denoise.rs:36
+    // this state as a portable record (NNN_STREAM_STATE_BYTES), and a state that continues from one (a batch slot's export_streams)
+    std::vector<uint8_t> export_state() const { return b_.export_streams({0}); }
+    static DenoiseState from_state(const std::vector<uint8_t> &record, const RnnModel *m = nullptr, int device = 0)
+    {
+        DenoiseState s(m, device);
+        s.b_.import_streams({0}, record);
+        return s;
+    }
 
   private:
     DenoiseState(const RnnModel *m, int device) : b_(BatchDenoiser::sized(1, 1, m, device)) {}   // one frame per call: sized for it

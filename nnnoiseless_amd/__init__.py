@@ -28,6 +28,7 @@ FRAME_SIZE = 480
 FREQ_SIZE = 481
 NB_BANDS = 22
 NB_FEATURES = 42
+from ._ffi import STREAM_STATE_BYTES, STREAM_STATE_VERSION, stream_state_field  # noqa: E402  (per-stream state records)
 
 _lib = None
 
@@ -194,6 +195,37 @@ class BatchDenoiser:
         buf = np.frombuffer(data, np.uint8)
         self._lib.check(self._lib.L.nnn_batch_load_state(self._h, _ffi.ptr(buf), buf.nbytes))
 
+    def reset_streams(self, idx):
+        """The listed streams back to DenoiseState::new() (include/nnn_batch.h nnn_batch_reset_streams); the others carry on untouched.
+        Enqueued in order with the processing calls; returns at once."""
+        a, p = _ffi.stream_list(idx)
+        self._lib.check(self._lib.L.nnn_batch_reset_streams(self._h, p, a.size))
+
+    def export_streams(self, idx):
+        """The listed streams' state as portable records: uint8 [len(idx), STREAM_STATE_BYTES] (record i belongs to idx[i]), importable
+        into any slot of any batch whose stream runs a model of the same GRU sizes."""
+        a, p = _ffi.stream_list(idx)
+        out = np.zeros((a.size, STREAM_STATE_BYTES), np.uint8)
+        self._lib.check(self._lib.L.nnn_batch_export_streams(self._h, p, a.size, _ffi.ptr(out), out.nbytes))
+        return out
+
+    def import_streams(self, idx, records):
+        """Stream idx[i] takes record i's state (from export_streams of this or any other batch, or DenoiseState.export_state)."""
+        a, p = _ffi.stream_list(idx)
+        r = _ffi.stream_records(records, a.size)
+        self._lib.check(self._lib.L.nnn_batch_import_streams(self._h, p, a.size, _ffi.ptr(r), r.nbytes))
+
+    def export_streams_device(self, idx, d_dst, hip_stream=0):
+        """Records into device memory at d_dst (an int, len(idx) * STREAM_STATE_BYTES bytes); asynchronous on hip_stream."""
+        a, p = _ffi.stream_list(idx)
+        self._lib.check(self._lib.L.nnn_batch_export_streams_device(self._h, p, a.size, d_dst, hip_stream))
+
+    def import_streams_device(self, idx, d_src, hip_stream=0):
+        """Records from device memory at d_src; asynchronous.  The records are checked on the device: a list with a bad record
+        writes nothing, and the next synchronize() raises."""
+        a, p = _ffi.stream_list(idx)
+        self._lib.check(self._lib.L.nnn_batch_import_streams_device(self._h, p, a.size, d_src, hip_stream))
+
     def set_taps(self, on):
         self._lib.check(self._lib.L.nnn_batch_set_taps(self._h, int(on)))
 
@@ -327,6 +359,17 @@ class DenoiseState:
     def clone(self):
         """`impl Clone for DenoiseState` (src/denoise.rs:36)."""
         return DenoiseState(_batch=self._b.clone())
+
+    def export_state(self):
+        """This state as a portable record (uint8 [STREAM_STATE_BYTES], include/nnn_batch.h): importable into a batch slot."""
+        return self._b.export_streams([0])[0]
+
+    @classmethod
+    def from_state(cls, record, model=None, device=0, lib=None):
+        """A state that continues from `record` (a batch slot's export_streams row, or export_state)."""
+        st = cls(model, device=device, lib=lib)
+        st._b.import_streams([0], np.asarray(record, np.uint8).reshape(1, -1))
+        return st
 
     @classmethod
     def new(cls, **kw):

@@ -21,6 +21,8 @@ BATCH_SYMBOLS = [
     "nnn_batch_kernel_name", "nnn_batch_read_kernel_times", "nnn_batch_set_graph", "nnn_batch_set_pipeline", "nnn_batch_read_stamps",
     "nnn_host_alloc", "nnn_host_free", "nnn_last_error", "nnn_batch_fault", "nnn_batch_debug_withhold_flag", "nnn_batch_set_frame_log",
     "nnn_batch_create_opts", "nnn_batch_max_group_frames", "nnn_batch_device_bytes", "nnn_batch_set_back_end", "nnn_device_local_cpulist",
+    "nnn_batch_reset_streams", "nnn_batch_export_streams", "nnn_batch_import_streams", "nnn_batch_export_streams_device",
+    "nnn_batch_import_streams_device",
 ]
 TRAIN_SYMBOLS = [
     "nnn_train_create", "nnn_train_destroy", "nnn_train_reset", "nnn_train_process_device", "nnn_train_process_host",
@@ -32,7 +34,7 @@ RESAMPLE_SYMBOLS = [
 NODE_SYMBOLS = [
     "nnn_node_create", "nnn_node_destroy", "nnn_node_num_streams", "nnn_node_num_shards", "nnn_node_shard", "nnn_node_batch", "nnn_node_reset",
     "nnn_node_process_host", "nnn_node_process_pcm_host", "nnn_node_process_device", "nnn_node_process_device_streams", "nnn_node_synchronize",
-    "nnn_node_fault", "nnn_node_shard_cpus",
+    "nnn_node_fault", "nnn_node_shard_cpus", "nnn_node_reset_streams", "nnn_node_export_streams", "nnn_node_import_streams",
 ]
 RNNOISE_SYMBOLS = [
     "rnnoise_get_frame_size", "rnnoise_get_size", "rnnoise_init", "rnnoise_create", "rnnoise_destroy",
@@ -41,6 +43,26 @@ RNNOISE_SYMBOLS = [
 
 
 PCM_F32, PCM_I16, PCM_F32_UNIT = 0, 1, 2
+
+# per-stream state records (include/nnn_batch.h NNN_STREAM_STATE_*): byte offsets of the fields
+STREAM_STATE_BYTES = 11232
+STREAM_STATE_VERSION = 1
+STREAM_STATE_MAGIC = 0x3153534E
+STREAM_STATE_FIELDS = {   # name: (byte offset, numpy dtype, count)
+    "magic": (0, np.uint32, 1), "version": (4, np.uint32, 1), "size": (8, np.uint32, 1), "gru_sizes": (12, np.int32, 3),
+    "mem_id": (24, np.int32, 1), "last_period": (28, np.int32, 1), "last_gain": (32, np.float32, 1), "mem_hp_x": (36, np.float32, 2),
+    "input_mem": (64, np.float32, 1728), "synthesis_mem": (6976, np.float32, 480), "cepstral_mem": (8896, np.float32, 176),
+    "lastg": (9600, np.float32, 22), "vad_gru": (9696, np.float32, 128), "noise_gru": (10208, np.float32, 128),
+    "denoise_gru": (10720, np.float32, 128),
+}
+
+
+def stream_state_field(records, name):
+    """A field of one record ([STREAM_STATE_BYTES] uint8) or of a stack of them ([n, STREAM_STATE_BYTES]) as numbers: [..., count]."""
+    off, dt, cnt = STREAM_STATE_FIELDS[name]
+    r = np.ascontiguousarray(records, dtype=np.uint8)
+    a = r[..., off:off + cnt * np.dtype(dt).itemsize].view(dt)
+    return a.reshape(r.shape[:-1] + (cnt,))
 PCM_DTYPE = {PCM_F32: np.float32, PCM_I16: np.int16, PCM_F32_UNIT: np.float32}
 
 
@@ -119,6 +141,18 @@ class Library:
         if hasattr(L, "nnn_batch_create_opts"):
             L.nnn_batch_create_opts.restype = vp
             L.nnn_batch_device_bytes.restype = sz
+        if hasattr(L, "nnn_batch_reset_streams"):
+            ip = C.POINTER(i32)
+            L.nnn_batch_reset_streams.argtypes = [vp, ip, i32]
+            L.nnn_batch_export_streams.argtypes = [vp, ip, i32, vp, sz]
+            L.nnn_batch_import_streams.argtypes = [vp, ip, i32, vp, sz]
+            L.nnn_batch_export_streams_device.argtypes = [vp, ip, i32, vp, vp]
+            L.nnn_batch_import_streams_device.argtypes = [vp, ip, i32, vp, vp]
+        if hasattr(L, "nnn_node_reset_streams"):
+            ip = C.POINTER(i32)
+            L.nnn_node_reset_streams.argtypes = [vp, ip, i32]
+            L.nnn_node_export_streams.argtypes = [vp, ip, i32, vp, sz]
+            L.nnn_node_import_streams.argtypes = [vp, ip, i32, vp, sz]
         if hasattr(L, "nnn_node_create"):
             L.nnn_node_create.restype = vp
             L.nnn_node_create.argtypes = [vp, i32, C.POINTER(i32), i32, C.POINTER(BatchOpts)]
@@ -173,3 +207,20 @@ def ptr(a):
 
 def as_f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def stream_list(idx):
+    """A stream index list as the int32 array the C ABI takes (host memory) and a pointer to it."""
+    a = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).reshape(-1))
+    if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+        raise ValueError("stream index out of int32 range")
+    a = a.astype(np.int32)
+    return a, a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def stream_records(records, n):
+    """n records as one C-contiguous uint8 block [n, STREAM_STATE_BYTES]."""
+    r = np.ascontiguousarray(records, dtype=np.uint8)
+    if r.size != n * STREAM_STATE_BYTES:
+        raise ValueError(f"need {n} records of {STREAM_STATE_BYTES} bytes, got {r.size} bytes")
+    return r.reshape(n, STREAM_STATE_BYTES)

@@ -209,6 +209,18 @@ struct nnn_batch {
     std::vector<int> evp_kernel;
     double k_ms[K_COUNT] = {0};
     int64_t k_launches[K_COUNT] = {0};
+    // per-stream state records (nnn_batch_*_streams), made on first use; none of it is counted in device_bytes or copied by snapshots
+    int *ss_dims = nullptr;            // device, per tile: the GRU sizes of its model, nv | nn << 8 | ndn << 16
+    int *ss_flag = nullptr;            // device: the record check of a device import found a bad record (the import kernel then writes nothing)
+    volatile int *ss_bad_host = nullptr;   // host view of the same verdict (page-locked, mapped): reported by nnn_batch_synchronize
+    int *ss_bad_dev = nullptr;
+    int *ss_idx = nullptr;             // device copy of a long scattered index list, and its page-locked source
+    int *ss_idx_pin = nullptr;
+    size_t ss_idx_cap = 0;
+    hipEvent_t ev_ss_idx = nullptr;    // the last copy out of ss_idx_pin is done
+    bool ss_idx_busy = false;
+    char *ss_stage = nullptr;          // the host variants' records on the device (grow-only)
+    size_t ss_stage_cap = 0;
 };
 
 template <class T> static hipError_t dalloc(nnn_batch *h, T **p, size_t count, bool is_state)
@@ -302,6 +314,13 @@ extern "C" void nnn_batch_destroy(nnn_batch *h)
     if (h->stage) hipFree(h->stage);
     if (h->stage_vad) hipFree(h->stage_vad);
     if (h->zc_host) hipHostFree(h->zc_host);
+    if (h->ss_dims) hipFree(h->ss_dims);
+    if (h->ss_flag) hipFree(h->ss_flag);
+    if (h->ss_bad_host) hipHostFree((void *)h->ss_bad_host);
+    if (h->ss_idx) hipFree(h->ss_idx);
+    if (h->ss_idx_pin) hipHostFree(h->ss_idx_pin);
+    if (h->ev_ss_idx) hipEventDestroy(h->ev_ss_idx);
+    if (h->ss_stage) hipFree(h->ss_stage);
     for (int i = 0; i < NSTREAMS; i++)
         if (h->pool[i]) hipStreamDestroy(h->pool[i]);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -646,6 +665,11 @@ extern "C" int nnn_batch_synchronize(nnn_batch *h)
     HIPCHK(hipSetDevice(h->device));
     if (h->have_last) HIPCHK(hipEventSynchronize(h->ev_last));   // the most recent call, whatever stream it was made on
     HIPCHK(hipStreamSynchronize(h->stream));
+    if (h->ss_bad_host && *h->ss_bad_host) {   // (reported once)
+        *h->ss_bad_host = 0;
+        return fail("nnn_batch_import_streams_device: a record did not match its target stream (magic, version, size or GRU sizes); "
+                    "that import wrote nothing");
+    }
     return report_fault(h);
 }
 
@@ -769,6 +793,447 @@ extern "C" nnn_batch *nnn_batch_clone(nnn_batch *h)
         return nullptr;
     }
     return c;
+}
+
+// ---- per-stream state records (include/nnn_batch.h, NNN_STREAM_STATE_*) ---------------------------------------------------------
+// A record is one stream's DenoiseState in the reference's terms.  Export reads the history ring through the batch's frame count
+// (input_mem comes out oldest first).  Import writes input_mem into the ring slots the next frame reads (frame_count - 1 and the
+// 1248 samples before it) and re-derives what the batch keeps beside the ring with the high-pass kernels' arithmetic (k_hp / k_hp2):
+// the decimated values of the last three frames (and their mirror), x_lp[0] of the next frame's slot and the last filtered sample --
+// the bits the batch itself would have made.  Nothing per-frame (lpc, lpc_head, the scratch sets, pflag) is touched: the next frame
+// remakes it before reading it, and k_pitch takes the last pitch of a call's first frame from last_period / last_gain, which the record
+// holds.  Records are handled as 32-bit words (bit copies; ints and floats alike).
+constexpr int SS_WORDS = NNN_STREAM_STATE_BYTES / 4;
+constexpr int SS_W_TI = NNN_STREAM_STATE_OFF_MEM_ID / 4;           // words 6 .. 10: mem_id, last_period, last_gain, mem_hp_x[2] (TI rows 0 .. 4)
+constexpr int SS_W_IN = NNN_STREAM_STATE_OFF_INPUT_MEM / 4;
+constexpr int SS_W_SYN = NNN_STREAM_STATE_OFF_SYNTHESIS_MEM / 4;
+constexpr int SS_W_CEPS = NNN_STREAM_STATE_OFF_CEPSTRAL_MEM / 4;    // ceps_mem then lastg: TI rows 5 .. 202
+constexpr int SS_W_GRU = NNN_STREAM_STATE_OFF_VAD_GRU / 4;
+constexpr int SS_GRU = 128;
+constexpr int SS_TI_ROWS = 5 + CEPS_MEM * NB + NB;
+constexpr int SS_DEC = 3 * 240;     // decimated values of frames frame_count - 3 .. - 1: what the next frame's 864-value window reaches back to
+constexpr int SS_DEC_X0 = HIST - 3 * FRAME;   // input_mem index of frame frame_count - 3's first sample
+constexpr int SS_SMALL = 32;        // index lists up to this long travel in the kernel arguments
+constexpr int SS_CHUNK = 96;        // samples per LDS chunk of the tile kernel's import
+static_assert(NNN_STREAM_STATE_OFF_LASTG / 4 == SS_W_CEPS + CEPS_MEM * NB && SS_W_GRU == SS_W_CEPS + CEPS_MEM * NB + NB + 2, "record layout");
+static_assert(SS_W_GRU + 3 * SS_GRU == SS_WORDS && SS_W_SYN == SS_W_IN + HIST && SS_W_CEPS == SS_W_SYN + FRAME, "record layout");
+static_assert(HIST % SS_CHUNK == 0 && SS_DEC_X0 % SS_CHUNK == 0 && FRAME % SS_CHUNK == 0, "chunking");
+
+struct SsArgs {
+    const int *dims;    // per tile: GRU sizes of its model, nv | nn << 8 | ndn << 16
+    const int *idx;     // mode 2: the index list in device memory
+    int small[SS_SMALL];   // mode 1
+    int mode;           // stream of entry i: 0 = first + i, 1 = small[i], 2 = idx[i]
+    int first, n;
+    int rb_in;          // ring position of input_mem[0] (newest frame in the slot before frame_count's)
+    int dec_row0;       // decimated-ring row of the first value of frame frame_count - 3
+    int slot_next;      // ring slot of frame frame_count
+    const int *flag;    // device import: != 0 = the record check refused the list (nothing is written)
+};
+__device__ __forceinline__ int ss_stream(const SsArgs &a, int i) { return a.mode == 0 ? a.first + i : (a.mode == 1 ? a.small[i] : a.idx[i]); }
+
+// the 32-bit word of TI row r (record order: mem_id, last_period, last_gain, mem_hp_x[0..1], ceps_mem[8][22], lastg[22]) of a stream
+__device__ __forceinline__ unsigned *ss_ti(const Buffers &b, int r, int tile, int lane)
+{
+    if (r == 0) return (unsigned *)NNN_TI(b.mem_id, 1, tile, lane);
+    if (r == 1) return (unsigned *)NNN_TI(b.last_period, 1, tile, lane);
+    if (r == 2) return (unsigned *)NNN_TI(b.last_gain, 1, tile, lane);
+    if (r < 5) return (unsigned *)(NNN_TI(b.hp_mem, 2, tile, lane) + (size_t)(r - 3) * TILE);
+    if (r < 5 + CEPS_MEM * NB) return (unsigned *)(NNN_TI(b.ceps_mem, CEPS_MEM * NB, tile, lane) + (size_t)(r - 5) * TILE);
+    return (unsigned *)(NNN_TI(b.lastg, NB, tile, lane) + (size_t)(r - 5 - CEPS_MEM * NB) * TILE);
+}
+// record word j -> TI row, or -1
+__device__ __forceinline__ int ss_ti_row(int j)
+{
+    if (j >= SS_W_TI && j < SS_W_TI + 5) return j - SS_W_TI;
+    if (j >= SS_W_CEPS && j < SS_W_CEPS + CEPS_MEM * NB + NB) return 5 + j - SS_W_CEPS;
+    return -1;
+}
+// stream s's GRU row k (0 vad, 1 noise, 2 denoise): rows of the model's own width inside a tile sized for the widest model
+__device__ __forceinline__ unsigned *ss_gru(const Buffers &b, int k, int s, int n)
+{
+    const size_t tile = (size_t)(s / TILE), r = (size_t)(s % TILE);
+    float *p = k == 0 ? b.gru_v + tile * TILE * b.gru_v_w : (k == 1 ? b.gru_n + tile * TILE * b.gru_n_w : b.gru_dn + tile * TILE * b.gru_dn_w);
+    return (unsigned *)(p + r * (size_t)n);
+}
+__device__ __forceinline__ size_t ss_hist_at(const Buffers &b, const SsArgs &a, int s, int i)   // input_mem[i] of stream s in the ring
+{
+    int p = a.rb_in + i;
+    if (p >= ring_len(b.nslot)) p -= ring_len(b.nslot);
+    return (size_t)s * hist_stride(b.nslot) + p;
+}
+// record word j of stream s, every word but the TI rows (ti = nullptr: those too, read one at a time)
+__device__ __forceinline__ unsigned ss_export_word(const Buffers &b, const SsArgs &a, int s, int j, int dims)
+{
+    if (j < SS_W_IN) {
+        const int r = ss_ti_row(j);
+        if (r >= 0) return *ss_ti(b, r, s / TILE, s % TILE);
+        if (j == 0) return NNN_STREAM_STATE_MAGIC;
+        if (j == 1) return NNN_STREAM_STATE_VERSION;
+        if (j == 2) return NNN_STREAM_STATE_BYTES;
+        if (j < 6) return (unsigned)((dims >> (8 * (j - 3))) & 255);
+        return 0u;
+    }
+    if (j < SS_W_SYN) return ((const unsigned *)b.hist)[ss_hist_at(b, a, s, j - SS_W_IN)];
+    if (j < SS_W_CEPS) return ((const unsigned *)b.synth_mem)[(size_t)s * FRAME + (j - SS_W_SYN)];
+    if (j < SS_W_GRU) {
+        const int r = ss_ti_row(j);
+        return r >= 0 ? *ss_ti(b, r, s / TILE, s % TILE) : 0u;
+    }
+    const int k = (j - SS_W_GRU) / SS_GRU, u = (j - SS_W_GRU) % SS_GRU, n = (dims >> (8 * k)) & 255;
+    return u < n ? ss_gru(b, k, s, n)[u] : 0u;
+}
+// record word j (value v) of stream s into the batch: everything but the TI rows and the derived values
+__device__ __forceinline__ void ss_import_word(const Buffers &b, const SsArgs &a, int s, int j, unsigned v, int dims)
+{
+    if (j < SS_W_IN) return;
+    if (j < SS_W_SYN) {
+        const size_t at = ss_hist_at(b, a, s, j - SS_W_IN);
+        ((unsigned *)b.hist)[at] = v;
+        if (at == (size_t)s * hist_stride(b.nslot)) ((unsigned *)b.hist)[at + ring_len(b.nslot)] = v;   // hist[ring_len] repeats hist[0]
+        return;
+    }
+    if (j < SS_W_CEPS) { ((unsigned *)b.synth_mem)[(size_t)s * FRAME + (j - SS_W_SYN)] = v; return; }
+    if (j < SS_W_GRU) return;
+    const int k = (j - SS_W_GRU) / SS_GRU, u = (j - SS_W_GRU) % SS_GRU, n = (dims >> (8 * k)) & 255;
+    if (u < n) ss_gru(b, k, s, n)[u] = v;
+}
+// decimated value k (0 .. SS_DEC) from input_mem x[SS_DEC_X0 + 2k - 1 .. + 1], as k_hp / k_hp2 make it, into its ring row (and the mirror)
+__device__ __forceinline__ void ss_dec_store(const Buffers &b, const SsArgs &a, int tile, int lane, int k, float xa, float xm, float xn)
+{
+    const int nslot = b.nslot;
+    int row = a.dec_row0 + k;
+    if (row >= dec_ring_len(nslot)) row -= dec_ring_len(nslot);
+    float *ring = NNN_TI(b.dec, dec_len(nslot), tile, lane);
+    const float dv = ((xa + xn) / 2.0f + xm) / 2.0f;
+    ring[(size_t)row * TILE] = dv;
+    if (row < DEC_MIRROR * 240) ring[(size_t)(dec_ring_len(nslot) + row) * TILE] = dv;
+}
+// x_lp[0] of the next frame (its window starts at input_mem[480]) and the last filtered sample
+__device__ __forceinline__ void ss_derived(const Buffers &b, const SsArgs &a, int tile, int lane, float x480, float x481, float x_last)
+{
+    NNN_TI(b.xlp0, b.nslot, tile, lane)[(size_t)a.slot_next * TILE] = (x481 / 2.0f + x480) / 2.0f;   // as hp_frame
+    NNN_TI(b.hp_last, 1, tile, lane)[0] = x_last;
+}
+
+// a few streams: one block of 256 threads per list entry
+__global__ void __launch_bounds__(256) k_ss_export_streams(Buffers b, SsArgs a, unsigned *dst)
+{
+    const int i = blockIdx.x, s = ss_stream(a, i), dims = a.dims[s / TILE];
+    unsigned *rec = dst + (size_t)i * SS_WORDS;
+    for (int j = threadIdx.x; j < SS_WORDS; j += 256) rec[j] = ss_export_word(b, a, s, j, dims);
+}
+// src = nullptr: the zero record (reset)
+__global__ void __launch_bounds__(256) k_ss_import_streams(Buffers b, SsArgs a, const unsigned *src)
+{
+    if (a.flag && a.flag[0]) return;
+    const int i = blockIdx.x, s = ss_stream(a, i), dims = a.dims[s / TILE], tile = s / TILE, lane = s % TILE;
+    const unsigned *rec = src ? src + (size_t)i * SS_WORDS : nullptr;
+    for (int j = threadIdx.x; j < SS_WORDS; j += 256) {
+        const unsigned v = rec ? rec[j] : 0u;
+        const int r = ss_ti_row(j);
+        if (r >= 0) *ss_ti(b, r, tile, lane) = v;
+        else ss_import_word(b, a, s, j, v, dims);
+    }
+    const float *x = rec ? (const float *)(rec + SS_W_IN) : nullptr;
+    for (int k = threadIdx.x; k < SS_DEC; k += 256) {
+        const int p = SS_DEC_X0 + 2 * k;
+        ss_dec_store(b, a, tile, lane, k, x ? x[p - 1] : 0.0f, x ? x[p] : 0.0f, x ? x[p + 1] : 0.0f);
+    }
+    if (threadIdx.x == 0) ss_derived(b, a, tile, lane, x ? x[FRAME] : 0.0f, x ? x[FRAME + 1] : 0.0f, x ? x[HIST - 1] : 0.0f);
+}
+
+// A contiguous run of streams (a migration, a whole batch): one block per tile, lane = stream on the TI rows (one 256-byte row per wave
+// instruction), the record's TI words transposed through LDS; the stream-major parts are contiguous runs of the record either way.
+__global__ void __launch_bounds__(256) k_ss_export_tiles(Buffers b, SsArgs a, unsigned *dst)
+{
+    __shared__ unsigned T[SS_TI_ROWS][TILE + 1];
+    const int tile = a.first / TILE + (int)blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int dims = a.dims[tile];
+    for (int r = wave; r < SS_TI_ROWS; r += 4) T[r][lane] = *ss_ti(b, r, tile, lane);
+    __syncthreads();
+    for (int q = 0; q < TILE; q++) {
+        const int s = tile * TILE + q;
+        if (s < a.first || s >= a.first + a.n) continue;
+        unsigned *rec = dst + (size_t)(s - a.first) * SS_WORDS;
+        for (int j = tid; j < SS_WORDS; j += 256) {
+            const int r = ss_ti_row(j);
+            rec[j] = r >= 0 ? T[r][q] : ss_export_word(b, a, s, j, dims);
+        }
+    }
+}
+__global__ void __launch_bounds__(256) k_ss_import_tiles(Buffers b, SsArgs a, const unsigned *src)
+{
+    __shared__ unsigned T[SS_TI_ROWS][TILE + 1];
+    __shared__ float X[TILE][SS_CHUNK + 1];   // a chunk of input_mem of every stream, and the sample before it (column 0)
+    if (a.flag && a.flag[0]) return;
+    const int tile = a.first / TILE + (int)blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int dims = a.dims[tile];
+    const int s_me = tile * TILE + lane;
+    const bool mine = s_me >= a.first && s_me < a.first + a.n;   // (lane = stream)
+    auto rec_of = [&](int q) { return src + (size_t)(tile * TILE + q - a.first) * SS_WORDS; };
+    auto listed = [&](int q) { const int s = tile * TILE + q; return s >= a.first && s < a.first + a.n; };
+    // TI rows: records -> LDS (each stream's words in runs) -> one row of 64 streams per store
+    for (int e = tid; e < TILE * SS_TI_ROWS; e += 256) {
+        const int q = e / SS_TI_ROWS, r = e - q * SS_TI_ROWS;
+        T[r][q] = (src && listed(q)) ? rec_of(q)[r < 5 ? SS_W_TI + r : SS_W_CEPS + r - 5] : 0u;
+    }
+    __syncthreads();
+    if (mine)
+        for (int r = wave; r < SS_TI_ROWS; r += 4) *ss_ti(b, r, tile, lane) = T[r][lane];
+    // overlap memory and GRU rows: runs of the record
+    for (int q = 0; q < TILE; q++) {
+        if (!listed(q)) continue;
+        const int s = tile * TILE + q;
+        for (int j = SS_W_SYN + tid; j < SS_W_CEPS; j += 256) ss_import_word(b, a, s, j, src ? rec_of(q)[j] : 0u, dims);
+        for (int j = SS_W_GRU + tid; j < SS_WORDS; j += 256) ss_import_word(b, a, s, j, src ? rec_of(q)[j] : 0u, dims);
+    }
+    // input_mem in chunks through LDS: the history ring (runs of each stream), the decimated ring (rows of 64 streams), x_lp[0], the last sample
+    for (int c = 0; c < HIST / SS_CHUNK; c++) {
+        __syncthreads();   // (the previous chunk has been read)
+        for (int e = tid; e < TILE * (SS_CHUNK + 1); e += 256) {
+            const int q = e / (SS_CHUNK + 1), i = e - q * (SS_CHUNK + 1), x = c * SS_CHUNK + i - 1;
+            X[q][i] = (src && listed(q) && x >= 0) ? ((const float *)rec_of(q))[SS_W_IN + x] : 0.0f;
+        }
+        __syncthreads();
+        for (int e = tid; e < TILE * SS_CHUNK; e += 256) {
+            const int q = e / SS_CHUNK, i = e - q * SS_CHUNK;
+            if (listed(q)) ss_import_word(b, a, tile * TILE + q, SS_W_IN + c * SS_CHUNK + i, __float_as_uint(X[q][i + 1]), dims);
+        }
+        if (mine && c * SS_CHUNK >= SS_DEC_X0)
+            for (int kl = wave; kl < SS_CHUNK / 2; kl += 4)
+                ss_dec_store(b, a, tile, lane, (c * SS_CHUNK - SS_DEC_X0) / 2 + kl, X[lane][2 * kl], X[lane][2 * kl + 1], X[lane][2 * kl + 2]);
+        if (mine && wave == 0 && c == FRAME / SS_CHUNK) NNN_TI(b.xlp0, b.nslot, tile, lane)[(size_t)a.slot_next * TILE] = (X[lane][2] / 2.0f + X[lane][1]) / 2.0f;
+        if (mine && wave == 0 && c == HIST / SS_CHUNK - 1) NNN_TI(b.hp_last, 1, tile, lane)[0] = X[lane][SS_CHUNK];
+    }
+}
+// a device import's records against their target streams (magic, version, size, GRU sizes): any mismatch drops the whole list
+__global__ void __launch_bounds__(256) k_ss_check(SsArgs a, const unsigned *src, int *flag, int *report)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const unsigned *rec = src + (size_t)i * SS_WORDS;
+    const int dims = a.dims[ss_stream(a, i) / TILE];
+    bool bad = rec[0] != NNN_STREAM_STATE_MAGIC || rec[1] != NNN_STREAM_STATE_VERSION || rec[2] != NNN_STREAM_STATE_BYTES;
+    for (int k = 0; k < 3; k++) bad = bad || rec[3 + k] != (unsigned)((dims >> (8 * k)) & 255);
+    if (bad) {   // (every writer writes the same value)
+        flag[0] = 1;
+        report[0] = 1;
+    }
+}
+
+static void ss_dims_host(const nnn_batch *h, int s, int d[3])
+{
+    for (const nnn_batch::ModelGroup &G : h->groups)
+        if (s / TILE >= G.tile0 && s / TILE < G.tile0 + G.ntiles) {
+            d[0] = G.plan.vad.n;
+            d[1] = G.plan.noise.n;
+            d[2] = G.plan.dn.n;
+            return;
+        }
+    d[0] = d[1] = d[2] = -1;
+}
+enum SsOp { SS_RESET = 0, SS_EXPORT = 1, SS_IMPORT = 2 };
+// Everything a call can check on the host, before it writes anything.  host_rec: an import's records in host memory (checked here),
+// or nullptr.  Also used by the node (nnn_node.cpp) to check every shard's part of a list before any shard is written.
+int nnn_batch_check_streams(const nnn_batch *h, int op, const int *streams, int n, const void *host_rec, size_t bytes, bool need_buf)
+{
+    if (!h) return fail("null batch");
+    if (n < 0) return fail("negative stream count");
+    if (n > 0 && !streams) return fail("null stream list");
+    if (op == SS_EXPORT && nnn_batch_fault(h)) return fail("export refused: the batch is faulted (nnn_batch_fault); its state is invalid");
+    if (need_buf && n > 0 && !host_rec) return fail("null record buffer");
+    if (need_buf && bytes < (size_t)n * NNN_STREAM_STATE_BYTES)
+        return fail("record buffer too small: %zu bytes for %d records of %d", bytes, n, NNN_STREAM_STATE_BYTES);
+    std::vector<char> seen(op == SS_EXPORT ? 0 : (size_t)h->S, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = streams[i];
+        if (s < 0 || s >= h->S) return fail("stream index %d (entry %d) outside [0, %d)", s, i, h->S);
+        if (op != SS_EXPORT) {
+            if (seen[(size_t)s]) return fail("stream %d listed twice", s);
+            seen[(size_t)s] = 1;
+        }
+    }
+    if (op == SS_IMPORT && host_rec)
+        for (int i = 0; i < n; i++) {
+            uint32_t w[6];
+            memcpy(w, (const char *)host_rec + (size_t)i * NNN_STREAM_STATE_BYTES, sizeof(w));
+            if (w[0] != NNN_STREAM_STATE_MAGIC) return fail("record %d: not a stream state record (magic %08x)", i, w[0]);
+            if (w[1] != NNN_STREAM_STATE_VERSION) return fail("record %d: version %u, this library reads version %d", i, w[1], NNN_STREAM_STATE_VERSION);
+            if (w[2] != NNN_STREAM_STATE_BYTES) return fail("record %d: size %u, expected %d", i, w[2], NNN_STREAM_STATE_BYTES);
+            int d[3];
+            ss_dims_host(h, streams[i], d);
+            if ((int)w[3] != d[0] || (int)w[4] != d[1] || (int)w[5] != d[2])
+                return fail("record %d: GRU sizes %d/%d/%d, stream %d's model has %d/%d/%d", i, (int)w[3], (int)w[4], (int)w[5], streams[i], d[0], d[1], d[2]);
+        }
+    return 0;
+}
+
+// first use: the per-tile GRU sizes, the check flag, the mapped report word
+static int ss_prepare(nnn_batch *h)
+{
+    HIPCHK(hipSetDevice(h->device));
+    if (h->ss_dims) return 0;
+    NNN_RT_LOCK;
+    std::vector<int> dims((size_t)h->NT, 0);
+    for (const nnn_batch::ModelGroup &G : h->groups)
+        for (int t = G.tile0; t < G.tile0 + G.ntiles; t++) dims[(size_t)t] = G.plan.vad.n | G.plan.noise.n << 8 | G.plan.dn.n << 16;
+    HIPCHK(hipMalloc((void **)&h->ss_flag, sizeof(int)));
+    HIPCHK(hipMemset(h->ss_flag, 0, sizeof(int)));
+    {
+        void *hp = nullptr, *dp = nullptr;
+        HIPCHK(hipHostMalloc(&hp, sizeof(int), hipHostMallocMapped));
+        *(volatile int *)hp = 0;
+        h->ss_bad_host = (volatile int *)hp;
+        HIPCHK(hipHostGetDevicePointer(&dp, hp, 0));
+        h->ss_bad_dev = (int *)dp;
+    }
+    HIPCHK(hipEventCreateWithFlags(&h->ev_ss_idx, hipEventDisableTiming));
+    int *d = nullptr;
+    HIPCHK(hipMalloc((void **)&d, dims.size() * sizeof(int)));
+    HIPCHK(hipMemcpy(d, dims.data(), dims.size() * sizeof(int), hipMemcpyHostToDevice));
+    h->ss_dims = d;
+    return 0;
+}
+// The stream of a state call, ordered after everything the batch has enqueued (as process_frames orders its calls); ss_end makes it
+// the batch's most recent call.  A pipelined call before it leaves prev_pipe set: cleared, so that the next call's high-pass does not
+// start early (nnn_batch_set_inputs_ready) on rings this call writes -- what nnn_batch_load_state does.
+static hipStream_t ss_begin(nnn_batch *h, void *hip_stream, bool &ok)
+{
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+    ok = !(h->have_last && h->last_stream != st) || hipStreamWaitEvent(st, h->ev_last, 0) == hipSuccess;
+    return st;
+}
+static int ss_end(nnn_batch *h, hipStream_t st)
+{
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev_last, st));
+    h->last_stream = st;
+    h->have_last = true;
+    h->prev_pipe = false;
+    return 0;
+}
+static int ss_args(nnn_batch *h, const int *streams, int n, hipStream_t st, SsArgs &a, bool &tiles)
+{
+    memset(&a, 0, sizeof(a));
+    a.dims = h->ss_dims;
+    a.n = n;
+    a.first = streams[0];
+    bool run = true;
+    for (int i = 1; i < n && run; i++) run = streams[i] == streams[0] + i;
+    tiles = run && n >= TILE;
+    if (run) a.mode = 0;
+    else if (n <= SS_SMALL) {
+        a.mode = 1;
+        for (int i = 0; i < n; i++) a.small[i] = streams[i];
+    } else {
+        a.mode = 2;
+        if ((size_t)n > h->ss_idx_cap) {
+            NNN_RT_LOCK;
+            if (int rc = quiesce(h)) return rc;   // (the old list may still be read)
+            if (h->ss_idx) HIPCHK(hipFree(h->ss_idx));
+            if (h->ss_idx_pin) HIPCHK(hipHostFree(h->ss_idx_pin));
+            h->ss_idx = nullptr;
+            h->ss_idx_pin = nullptr;
+            h->ss_idx_cap = 0;
+            h->ss_idx_busy = false;
+            HIPCHK(hipMalloc((void **)&h->ss_idx, (size_t)n * sizeof(int)));
+            HIPCHK(hipHostMalloc((void **)&h->ss_idx_pin, (size_t)n * sizeof(int), 0));
+            h->ss_idx_cap = (size_t)n;
+        }
+        if (h->ss_idx_busy) HIPCHK(hipEventSynchronize(h->ev_ss_idx));   // the page-locked list of the previous call has been copied
+        memcpy(h->ss_idx_pin, streams, (size_t)n * sizeof(int));
+        HIPCHK(hipMemcpyAsync(h->ss_idx, h->ss_idx_pin, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(h->ev_ss_idx, st));
+        h->ss_idx_busy = true;
+        a.idx = h->ss_idx;
+    }
+    const int nslot = h->nslot, N = (int)(h->frame_count % (uint64_t)nslot);
+    a.rb_in = ring_base((N + nslot - 1) % nslot, nslot);
+    a.dec_row0 = 240 * ((N + nslot - 3) % nslot);
+    a.slot_next = N;
+    return 0;
+}
+static void ss_launch(nnn_batch *h, bool to_records, const SsArgs &a, bool tiles, const void *src, void *dst, hipStream_t st)
+{
+    const Buffers &b = h->b[0];
+    const unsigned grid = tiles ? (unsigned)((a.first + a.n - 1) / TILE - a.first / TILE + 1) : (unsigned)a.n;
+    if (to_records) {
+        if (tiles) hipLaunchKernelGGL(k_ss_export_tiles, dim3(grid), dim3(256), 0, st, b, a, (unsigned *)dst);
+        else hipLaunchKernelGGL(k_ss_export_streams, dim3(grid), dim3(256), 0, st, b, a, (unsigned *)dst);
+    } else {
+        if (tiles) hipLaunchKernelGGL(k_ss_import_tiles, dim3(grid), dim3(256), 0, st, b, a, (const unsigned *)src);
+        else hipLaunchKernelGGL(k_ss_import_streams, dim3(grid), dim3(256), 0, st, b, a, (const unsigned *)src);
+    }
+}
+static int ss_stage(nnn_batch *h, size_t bytes)
+{
+    if (bytes <= h->ss_stage_cap) return 0;
+    NNN_RT_LOCK;
+    if (h->ss_stage) HIPCHK(hipFree(h->ss_stage));   // (host variants wait for their work: nothing reads it now)
+    h->ss_stage = nullptr;
+    h->ss_stage_cap = 0;
+    HIPCHK(hipMalloc((void **)&h->ss_stage, bytes));
+    h->ss_stage_cap = bytes;
+    return 0;
+}
+// one state call: checks, ordering, list, kernels (to_records: export), optional copies of the host variants
+static int ss_call(nnn_batch *h, SsOp op, const int *streams, int n, const void *host_src, void *host_dst, const void *d_src, void *d_dst,
+                   void *hip_stream, bool device_check)
+{
+    if (n == 0) return 0;
+    if (int rc = ss_prepare(h)) return rc;
+    const size_t bytes = (size_t)n * NNN_STREAM_STATE_BYTES;
+    if ((host_src || host_dst) && ss_stage(h, bytes)) return 1;
+    bool ok = true;
+    hipStream_t st = ss_begin(h, hip_stream, ok);
+    if (!ok) return fail("could not order the call after the batch's earlier work: %s", hipGetErrorString(hipGetLastError()));
+    SsArgs a;
+    bool tiles = false;
+    if (int rc = ss_args(h, streams, n, st, a, tiles)) return rc;
+    if (host_src) {
+        HIPCHK(hipMemcpyAsync(h->ss_stage, host_src, bytes, hipMemcpyHostToDevice, st));
+        d_src = h->ss_stage;
+    }
+    if (device_check) {
+        HIPCHK(hipMemsetAsync(h->ss_flag, 0, sizeof(int), st));
+        hipLaunchKernelGGL(k_ss_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, (const unsigned *)d_src, h->ss_flag, h->ss_bad_dev);
+        a.flag = h->ss_flag;
+    }
+    if (op == SS_EXPORT) ss_launch(h, true, a, tiles, nullptr, host_dst ? (void *)h->ss_stage : d_dst, st);
+    else ss_launch(h, false, a, tiles, op == SS_RESET ? nullptr : d_src, nullptr, st);
+    if (host_dst) HIPCHK(hipMemcpyAsync(host_dst, h->ss_stage, bytes, hipMemcpyDeviceToHost, st));
+    if (int rc = ss_end(h, st)) return rc;
+    if (host_src || host_dst) HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int nnn_batch_reset_streams(nnn_batch *h, const int *streams, int n)
+{
+    if (int rc = nnn_batch_check_streams(h, SS_RESET, streams, n, nullptr, 0, false)) return rc;
+    return ss_call(h, SS_RESET, streams, n, nullptr, nullptr, nullptr, nullptr, nullptr, false);
+}
+extern "C" int nnn_batch_export_streams(nnn_batch *h, const int *streams, int n, void *host_dst, size_t dst_bytes)
+{
+    if (int rc = nnn_batch_check_streams(h, SS_EXPORT, streams, n, host_dst, dst_bytes, true)) return rc;
+    return ss_call(h, SS_EXPORT, streams, n, nullptr, host_dst, nullptr, nullptr, nullptr, false);
+}
+extern "C" int nnn_batch_import_streams(nnn_batch *h, const int *streams, int n, const void *host_src, size_t src_bytes)
+{
+    if (int rc = nnn_batch_check_streams(h, SS_IMPORT, streams, n, host_src, src_bytes, true)) return rc;
+    return ss_call(h, SS_IMPORT, streams, n, host_src, nullptr, nullptr, nullptr, nullptr, false);
+}
+extern "C" int nnn_batch_export_streams_device(nnn_batch *h, const int *streams, int n, void *d_dst, void *hip_stream)
+{
+    if (int rc = nnn_batch_check_streams(h, SS_EXPORT, streams, n, nullptr, 0, false)) return rc;
+    if (n > 0 && (!d_dst || ((uintptr_t)d_dst & 3))) return fail("null or unaligned record buffer");
+    return ss_call(h, SS_EXPORT, streams, n, nullptr, nullptr, nullptr, d_dst, hip_stream, false);
+}
+extern "C" int nnn_batch_import_streams_device(nnn_batch *h, const int *streams, int n, const void *d_src, void *hip_stream)
+{
+    if (int rc = nnn_batch_check_streams(h, SS_IMPORT, streams, n, nullptr, 0, false)) return rc;
+    if (n > 0 && (!d_src || ((uintptr_t)d_src & 3))) return fail("null or unaligned record buffer");
+    return ss_call(h, SS_IMPORT, streams, n, nullptr, nullptr, d_src, nullptr, hip_stream, true);
 }
 
 // ---- one group of frames ------------------------------------------------------------------------

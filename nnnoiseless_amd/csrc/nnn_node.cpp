@@ -325,3 +325,81 @@ extern "C" int nnn_node_fault(const nnn_node *n)
         if (nnn_batch_fault(s.b)) return 1;
     return 0;
 }
+
+// ---- per-stream state records by node-global index --------------------------------------------------------------------------------
+// The list is split by shard (part k: the shard-local indices, and where each entry sits in the caller's list); every part is checked on
+// its shard before any shard is written.
+int nnn_batch_check_streams(const nnn_batch *h, int op, const int *streams, int n, const void *host_rec, size_t bytes, bool need_buf);   // nnn_batch.hip
+enum { NODE_SS_RESET = 0, NODE_SS_EXPORT = 1, NODE_SS_IMPORT = 2 };   // (nnn_batch.hip's SsOp)
+static int node_split(const nnn_node *n, const int *streams, int n_list, std::vector<std::vector<int>> &local, std::vector<std::vector<int>> &at)
+{
+    if (!n) return nnn_set_error("null node");
+    if (n_list < 0) return nnn_set_error("negative stream count");
+    if (n_list > 0 && !streams) return nnn_set_error("null stream list");
+    local.assign(n->shards.size(), {});
+    at.assign(n->shards.size(), {});
+    for (int i = 0; i < n_list; i++) {
+        const int s = streams[i];
+        if (s < 0 || s >= n->n_streams) {
+            char t[96];
+            snprintf(t, sizeof(t), "stream index %d (entry %d) outside [0, %d)", s, i, n->n_streams);
+            return nnn_set_error(t);
+        }
+        size_t k = 0;
+        while (s >= n->shards[k].hi) k++;   // (shards are contiguous and in order)
+        local[k].push_back(s - n->shards[k].lo);
+        at[k].push_back(i);
+    }
+    return 0;
+}
+
+extern "C" int nnn_node_reset_streams(nnn_node *n, const int *streams, int n_list)
+{
+    std::vector<std::vector<int>> local, at;
+    if (int rc = node_split(n, streams, n_list, local, at)) return rc;
+    for (size_t k = 0; k < local.size(); k++)
+        if (int rc = nnn_batch_check_streams(n->shards[k].b, NODE_SS_RESET, local[k].data(), (int)local[k].size(), nullptr, 0, false)) return rc;
+    for (size_t k = 0; k < local.size(); k++)
+        if (!local[k].empty())
+            if (int rc = nnn_batch_reset_streams(n->shards[k].b, local[k].data(), (int)local[k].size())) return rc;
+    return 0;
+}
+
+extern "C" int nnn_node_export_streams(nnn_node *n, const int *streams, int n_list, void *host_dst, size_t dst_bytes)
+{
+    std::vector<std::vector<int>> local, at;
+    if (int rc = node_split(n, streams, n_list, local, at)) return rc;
+    if (n_list > 0 && !host_dst) return nnn_set_error("null record buffer");
+    if (dst_bytes < (size_t)n_list * NNN_STREAM_STATE_BYTES) return nnn_set_error("record buffer too small");
+    for (size_t k = 0; k < local.size(); k++)
+        if (int rc = nnn_batch_check_streams(n->shards[k].b, NODE_SS_EXPORT, local[k].data(), (int)local[k].size(), nullptr, 0, false)) return rc;
+    std::vector<unsigned char> part;
+    for (size_t k = 0; k < local.size(); k++) {
+        if (local[k].empty()) continue;
+        part.resize(local[k].size() * NNN_STREAM_STATE_BYTES);
+        if (int rc = nnn_batch_export_streams(n->shards[k].b, local[k].data(), (int)local[k].size(), part.data(), part.size())) return rc;
+        for (size_t j = 0; j < at[k].size(); j++)
+            memcpy((char *)host_dst + (size_t)at[k][j] * NNN_STREAM_STATE_BYTES, part.data() + j * NNN_STREAM_STATE_BYTES, NNN_STREAM_STATE_BYTES);
+    }
+    return 0;
+}
+
+extern "C" int nnn_node_import_streams(nnn_node *n, const int *streams, int n_list, const void *host_src, size_t src_bytes)
+{
+    std::vector<std::vector<int>> local, at;
+    if (int rc = node_split(n, streams, n_list, local, at)) return rc;
+    if (n_list > 0 && !host_src) return nnn_set_error("null record buffer");
+    if (src_bytes < (size_t)n_list * NNN_STREAM_STATE_BYTES) return nnn_set_error("record buffer too small");
+    std::vector<std::vector<unsigned char>> parts(local.size());
+    for (size_t k = 0; k < local.size(); k++) {
+        parts[k].resize(local[k].size() * NNN_STREAM_STATE_BYTES);
+        for (size_t j = 0; j < at[k].size(); j++)
+            memcpy(parts[k].data() + j * NNN_STREAM_STATE_BYTES, (const char *)host_src + (size_t)at[k][j] * NNN_STREAM_STATE_BYTES, NNN_STREAM_STATE_BYTES);
+        if (int rc = nnn_batch_check_streams(n->shards[k].b, NODE_SS_IMPORT, local[k].data(), (int)local[k].size(), parts[k].data(), parts[k].size(), true))
+            return rc;
+    }
+    for (size_t k = 0; k < local.size(); k++)
+        if (!local[k].empty())
+            if (int rc = nnn_batch_import_streams(n->shards[k].b, local[k].data(), (int)local[k].size(), parts[k].data(), parts[k].size())) return rc;
+    return 0;
+}

@@ -94,6 +94,23 @@ class NodeDenoiser:
     def fault(self):
         return bool(self._lib.L.nnn_node_fault(self._h))
 
+    def reset_streams(self, idx):
+        """Node-global streams back to DenoiseState::new(), each on the shard that holds it (include/nnn_node.h)."""
+        a, p = _ffi.stream_list(idx)
+        self._lib.check(self._lib.L.nnn_node_reset_streams(self._h, p, a.size))
+
+    def export_streams(self, idx):
+        """Portable records of node-global streams, uint8 [len(idx), STREAM_STATE_BYTES] (BatchDenoiser.export_streams)."""
+        a, p = _ffi.stream_list(idx)
+        out = np.zeros((a.size, _ffi.STREAM_STATE_BYTES), np.uint8)
+        self._lib.check(self._lib.L.nnn_node_export_streams(self._h, p, a.size, _ffi.ptr(out), out.nbytes))
+        return out
+
+    def import_streams(self, idx, records):
+        a, p = _ffi.stream_list(idx)
+        r = _ffi.stream_records(records, a.size)
+        self._lib.check(self._lib.L.nnn_node_import_streams(self._h, p, a.size, _ffi.ptr(r), r.nbytes))
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.L.nnn_node_destroy(self._h)
