@@ -21,7 +21,7 @@ def make_training_inputs(seed, n_streams, n_frames):
     return sig, noise, comb, cutoff, vad
 
 
-def check_rows(rows, ref, ref32=None):
+def check_rows(rows, ref, ref32=None, feature_spread=False):
     """Cepstral / delta / variability features within 2e-4 absolute (values of order 1..20; the oracle's own f32-FFT and
     f64-FFT builds differ by up to 4e-5 on them).  The six pitch-correlation features (columns 34..39: band correlation /
     sqrt(.001 + Ex Ep)) are ill-conditioned on bands that hold only rounding noise -- the two oracle builds differ by up
@@ -33,7 +33,11 @@ def check_rows(rows, ref, ref32=None):
     assert np.array_equal(rows[..., 42:64] == -1.0, ref[..., 42:64] == -1.0)
     assert np.array_equal((rows[..., :42] == 0).all(axis=-1), (ref[..., :42] == 0).all(axis=-1))
     d = np.abs(rows[..., :42] - ref[..., :42]).max(axis=tuple(range(rows.ndim - 1)))
-    assert np.delete(d, slice(34, 40)).max() < 2e-4, d
+    if feature_spread:   # (inputs far above int16 scale, where the oracle's own two builds are further apart than the absolute bars: 3 x that spread)
+        d32 = np.abs(ref32[..., :42] - ref[..., :42]).max(axis=tuple(range(rows.ndim - 1)))
+        assert (np.delete(d, slice(34, 40)) <= np.maximum(2e-4, 3.0 * np.delete(d32, slice(34, 40)))).all(), (d, d32)
+    else:
+        assert np.delete(d, slice(34, 40)).max() < 2e-4, d
     if ref32 is not None:
         # rows are [frame][stream][87].  The yardstick is what f32 rounding in the FFT alone does to these quotients of two
         # noise-floor energies: the oracle's own f32-FFT build against its f64-FFT build.  As a whole the device's error must
@@ -55,5 +59,12 @@ def check_rows(rows, ref, ref32=None):
               f"({np.sqrt((e_o32 ** 2).mean()):.2e}); {len(over5)} of {err.size} streams beyond 5 x their own spread, worst at {(err / np.maximum(spread, 4e-5)).max():.1f} x")
     else:
         assert d[34:40].max() < 4e-2, d
+    if feature_spread:   # (the rms of columns 34..39 is held to the f32 build's above; gains and log levels as those six columns are:
+        # worst case and rms within 1.25 x the f32 build's, column by column within 5 x its spread)
+        e_dev, e_o32 = np.abs(rows[..., 42:86] - ref[..., 42:86]), np.abs(ref32[..., 42:86] - ref[..., 42:86])
+        assert e_dev.max() <= 1.25 * e_o32.max() and np.sqrt((e_dev ** 2).mean()) <= 1.25 * np.sqrt((e_o32 ** 2).mean())
+        e, e32 = (a.max(axis=tuple(range(rows.ndim - 1))) for a in (e_dev, e_o32))
+        assert (e <= np.maximum(1e-4, 5.0 * e32)).all(), (e, e32)
+        return
     assert np.sqrt(((rows[..., 34:40] - ref[..., 34:40]) ** 2).mean()) < 5e-4
     assert np.abs(rows[..., 42:86] - ref[..., 42:86]).max() < 1e-4
