@@ -283,7 +283,7 @@ int nnn_batch_set_schedule(nnn_batch *b, int mode, int lanes);
  * one note on stderr per process when batches are driven side by side on a device without it (they largely serialise on 4 queues).
  *   NNN_SCHED=seq|lanes|stages   how a call of 32 frames or more uses the batch's internal streams (nnn_batch_set_schedule)   test_hostsim_knobs
  *   NNN_LANES=1..4               lanes of the "lanes" schedule                                                                  test_hostsim_knobs
- *   NNN_HOST_CHUNK=n             frames per chunk of a host-buffer call (0 = one piece; default by call length)               test_gpu_parity / test_hostsim_pcm
+ *   NNN_HOST_CHUNK=n             host-buffer calls staged, n frames per chunk, 0 = one piece (unset: small calls zero-copy)   test_gpu_parity / test_hostsim_pcm
  *   NNN_RNN_ROWS=16|32           stream rows per RNN workgroup (default by model and batch size)                              test_gpu_parity / test_hostsim_parity
  *   NNN_RNN_WF_MIN_G=n           shortest frame group the layer-pipelined RNN kernel takes                                    test_gpu_parity / test_hostsim_parity
  *   NNN_HP_SPLIT=0|1             the high-pass on one wave per 64 streams or two (default: two for launches of <= 256 tiles)  test_gpu_back_end / test_hostsim_parity
@@ -291,8 +291,9 @@ int nnn_batch_set_schedule(nnn_batch *b, int mode, int lanes);
  *   NNN_PITCH_CHAIN=0|1|2        frames of a group side by side in k_pitch with a flag hand-off, or looped (default by size)  test_gpu_parity / test_hostsim_parity
  *   NNN_NODE_THREADS=0           a node's shards one after the other on the caller's thread                                   test_hostsim_node
  *   NNN_DEVICE=n                 HIP device of the rnnoise_* single-stream surface (default 0)                                 test_gpu_node
- * Earlier rounds' A/B probe knobs (NNN_BACK, NNN_HP_TPB, NNN_X_RIDES, NNN_LPC_IN_PITCH, NNN_HP_AFTER, NNN_PIPE_MAX, ...) exist only in
- * builds with -DNNN_DEV_KNOBS (the tests' interpreter build, scripts/build_variant*.sh); the product does not read them.
+ * Earlier rounds' A/B probe knobs are gone but for four that let the tests force a path: NNN_HP_TPB, NNN_X_RIDES, NNN_LPC_WIDE and
+ * NNN_LPC_FC.  They exist only in builds with -DNNN_DEV_KNOBS (the tests' interpreter build, scripts/build_variant*.sh); the product
+ * does not read them.
  */
 
 /* Diagnostic: the device's activation functions on their own, y[i] = act(x[i]) for n host floats; act 0 = tansig_approx,

@@ -481,10 +481,6 @@ __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0,
             transform_inputs<true, true, XR>(bf, sp, tile, 0, t, Z, part, &K);
             pitch = NNN_TI(bf.pitch, 1, tile, sl)[0];
             silent = __builtin_amdgcn_readfirstlane(K.silent) != 0;
-#ifdef NNN_PROBE_BACK_NOHOLD   // (developer probe, wrong audio, timing only: what the stretch costs when the spectra need not be kept)
-#pragma unroll
-            for (int u = 0; u < 8; u++) { K.X[u] = make_float2((float)u, 1.0f); K.P[u] = make_float2(1.0f, (float)u); }
-#endif
         } else {
             const float cv = lane < 28 ? NNN_TI(bf.cn, 28, tile, sl)[(size_t)lane * TILE] : 0.0f;
             pitch = NNN_TI(bf.pitch, 1, tile, sl)[0];
@@ -515,14 +511,10 @@ __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0,
                 *(uint4 *)(IN + (size_t)plx * in_ps + row * pl.in_w + 8 * c8) = v;
             }
         }
-        // the weight fragments of a phase are requested before the barrier that opens it (see BkW); NNN_BK_PREFETCH_FUSED=0 builds the fused
-        // kernel without (measured: 61.3 against 59.2 us per one-frame launch at 4096 streams -- the registers the prefetch takes are not
-        // what makes the fused kernel spill its spectra)
-#ifndef NNN_BK_PREFETCH_FUSED
-#define NNN_BK_PREFETCH_FUSED 1
-#endif
-        constexpr bool PF = !FUSED || NNN_BK_PREFETCH_FUSED;
-#define BK_EDGE(LOAD) do { if (PF) { LOAD; lds_barrier(); } else { lds_barrier(); LOAD; } } while (0)
+        // the weight fragments of a phase are requested before the barrier that opens it (see BkW), in the fused kernel too (measured
+        // without: 61.3 against 59.2 us per one-frame launch at 4096 streams -- the registers the prefetch takes are not what makes the
+        // fused kernel spill its spectra)
+#define BK_EDGE(LOAD) do { LOAD; lds_barrier(); } while (0)
         BkW W;
         BkH H;
         BK_EDGE(bk_dense_load(pl.dense, Wq, fpar, wave, lane, W));

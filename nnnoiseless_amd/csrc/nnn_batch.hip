@@ -86,8 +86,9 @@ int nnn_set_error(const char *msg) { return fail("%s", msg); }   // for the libr
 // round 4 a constructor exported it; VERDICT r4 #7b).  INTEGRATION.md tells real-time hosts to export GPU_MAX_HW_QUEUES=8 themselves.
 
 // Run-time knobs.  The default build reads exactly the environment variables of the table in include/nnn_batch.h ("Environment"), each at
-// batch creation and each exercised by a test.  Everything else is a developer knob (A/B probes of earlier rounds), compiled in only with
-// -DNNN_DEV_KNOBS -- the interpreter build of the tests and scripts/build_variant*.sh define it -- and absent from the product.
+// batch creation and each exercised by a test.  Four more are developer knobs that let the tests force a path (NNN_HP_TPB, NNN_X_RIDES,
+// NNN_LPC_WIDE, NNN_LPC_FC), compiled in only with -DNNN_DEV_KNOBS -- the interpreter build of the tests and scripts/build_variant*.sh
+// define it -- and absent from the product.
 static const char *knob(const char *name) { return getenv(name); }
 #ifdef NNN_DEV_KNOBS
 static const char *dev_knob(const char *name) { return getenv(name); }
@@ -106,6 +107,7 @@ constexpr int NSTREAMS = 5;    // internal streams of a pipelined call
 constexpr int EVR = 16;        // event ring: groups of one call that may still be referred to
 enum SchedMode { SCHED_SEQ = 0, SCHED_LANES = 1, SCHED_STAGES = 2 };
 constexpr int AUTO_BIG = 16384;   // streams above which the automatic schedule changes (process_frames)
+constexpr long long HANDOFF_TICKS = 10000ll * 100000ll;   // Buffers::handoff_ticks outside the test hook: 10 s of the 100 MHz clock
 
 struct nnn_batch {
     Buffers b[NSET];               // same state, NSET scratch sets (views into one allocation per scratch array: set s lies
@@ -132,7 +134,7 @@ struct nnn_batch {
     int back_mode = -1;            // the fused back end (k_back, nnn_back.hip): 0 = never, 1 = one-frame groups (the real-time tick), 2 = every group;
                                    // 3 / 4 = its RNN stretch alone (k_back<false>) in place of k_rnn / k_rnn_wf for one-frame / all groups;
                                    // -1 = by measurement (back_choice): one-frame groups only, fused up to 8192 streams, the RNN stretch
-                                   // alone above that or with other batches ticking beside this one (env NNN_BACK)
+                                   // alone above that or with other batches ticking beside this one (nnn_batch_set_back_end)
     int rnn_rows = 0;              // forced rows per RNN block (env NNN_RNN_ROWS), 0 = by model size and batch size
     std::vector<ModelGroup> groups;
     std::vector<RNNModel> models;  // host copies of the resident models (clone)
@@ -159,8 +161,8 @@ struct nnn_batch {
     hipStream_t copy_in = nullptr, copy_out = nullptr;   // host-buffer calls in chunks: uploads, downloads (created on first use)
     std::vector<hipEvent_t> ev_up, ev_run;               // per chunk: uploaded, processed
     int wf_min_g = 0;               // groups shorter than this run k_rnn instead of the layer-pipelined kernel (env NNN_RNN_WF_MIN_G; 0 = by batch size)
-    int host_chunk = -1;            // frames per chunk of a host-buffer call (env NNN_HOST_CHUNK): -1 = by call length and size,
-                                    // 0 = the whole call in one piece
+    int host_chunk = -1;            // frames per chunk of a host-buffer call (env NNN_HOST_CHUNK): -1 = by call length and size (small
+                                    // calls zero-copy), 0 = the whole call in one piece; set, it always takes the staged path
     StepParams *sp_tab = nullptr;   // device, per-frame parameter table of a call
     int sp_tab_cap = 0;
     hipStream_t stream = nullptr;   // default launch stream
@@ -178,7 +180,6 @@ struct nnn_batch {
     std::vector<int> prev_first;
     bool inputs_ready = false;      // the caller's promise that a call's input is final when the call is made
     volatile int *fault_host = nullptr;   // host view of Buffers::fault (page-locked, mapped): a hand-off that never arrived
-    long long handoff_ticks = 0;    // Buffers::handoff_ticks outside the test hook
     unsigned tickets = 0;           // work items handed out so far by chained k_pitch launches (Buffers::ticket never restarts)
     unsigned *frame_log = nullptr;  // nnn_batch_set_frame_log: the next frame's record (device), and the frames that still have room
     size_t frame_log_left = 0;
@@ -200,10 +201,8 @@ struct nnn_batch {
                                     // (measured at 4096 streams x 48 frames: 1: 28.5, 2: 37.1, 3: 32.9, 4: 32.2 M frames/s -- the default 4 hardware
                                     // queues are shared with the host's own streams)
     int pitch_chain = 1;            // k_pitch: one workgroup per (frame, quarter tile) instead of a frame loop: 1 = below 16384 streams, 0 = never, 2 = always (env NNN_PITCH_CHAIN)
-    int ramp = 0;                   // pipelined calls start and end with smaller groups (env NNN_RAMP=1; round 2a's default: with the
-                                    // frames of a group side by side in k_pitch and 16-frame groups, full groups throughout measured 6 % faster)
     bool taps_alloc = false;        // the tap-only scratch arrays exist
-    bool use_pipeline = true;
+    bool use_pipeline = true;       // nnn_batch_set_pipeline
     bool profiling = false;
     std::vector<hipEvent_t> evp;    // pairs per launch while profiling
     std::vector<int> evp_kernel;
@@ -344,21 +343,9 @@ static size_t rnn_wf_lds_bytes(const WfPlan &w)
     const size_t cols = (size_t)w.w_v + 2 * w.w_n + 3 * w.w_dn + 2 * ((size_t)w.sw_v + w.sw_n + w.sw_dn) + WF_FS_W;
     return (256 + 128) * 4 + (size_t)3 * WF_ROWS * cols * 2 + (size_t)(CEPS_MEM * NB + 28 + 28) * WF_ROWS * 4;
 }
-static bool rnn_wf_enabled()
-{
-    const char *e = dev_knob("NNN_RNN_WF");
-    return !e || atoi(e) != 0;
-}
 // below this many RNN blocks a launch leaves compute units idle and the per-block chain dominates
-static int rnn_small_batch_blocks()
-{
-    static int v = -1;
-    if (v < 0) {
-        const char *e = dev_knob("NNN_RNN_MIN_BLOCKS");
-        v = e ? atoi(e) : 128;   // measured at 1024 / 4096 / 16384 streams (profiles/r1_e_rnn_rows.txt)
-    }
-    return v;
-}
+// (measured at 1024 / 4096 / 16384 streams, profiles/r1_e_rnn_rows.txt)
+constexpr int RNN_SMALL_BATCH_BLOCKS = 128;
 
 static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *group_streams, int n_groups, int device, int gmax)
 {
@@ -386,11 +373,8 @@ static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *g
             for (int i = 0; i < EVR; i++) HIPCHK(hipEventCreateWithFlags(&h->ev[p][s][i], hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&h->ev_done[p], hipEventDisableTiming));
     }
-    if (const char *e = dev_knob("NNN_PIPELINE")) h->use_pipeline = atoi(e) != 0;
-    if (const char *e = dev_knob("NNN_RAMP")) h->ramp = atoi(e);
     if (const char *e = knob("NNN_HOST_CHUNK")) h->host_chunk = atoi(e);
     if (const char *e = knob("NNN_RNN_WF_MIN_G")) h->wf_min_g = atoi(e);
-    if (const char *e = dev_knob("NNN_BACK")) h->back_mode = atoi(e);
     if (const char *e = knob("NNN_HP_SPLIT")) h->hp_split = atoi(e);
     if (const char *e = dev_knob("NNN_HP_TPB")) h->hp_tpb = atoi(e);
     if (const char *e = knob("NNN_LPC_HEAD")) h->lpc_head = atoi(e);
@@ -416,7 +400,6 @@ static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *g
     // groups in flight behind the high-pass: what the schedule chosen at creation can use (a schedule set later works on what is there).
     // Nobody choosing, batches above AUTO_BIG streams keep two groups in flight (round 6, see process_frames: their calls overlap kernels).
     h->depth = (h->n_lanes >= 2 || h->sched == SCHED_STAGES || (h->sched_auto && (n_streams + TILE - 1) / TILE * TILE > AUTO_BIG)) ? DEPTH : 1;
-    if (const char *e = dev_knob("NNN_RING_DEPTH")) h->depth = atoi(e) >= 2 ? DEPTH : 1;   // (experiment knob)
     h->nset = h->depth * h->gmax;
     h->nslot = slots_for(h->gmax, h->depth);
     h->S = n_streams;
@@ -452,7 +435,7 @@ static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *g
         for (int rows = 32; rows >= 16 && !G.rows; rows /= 2)   // (64 rows never fit: the states stay in LDS for a whole group)
             if (rnn_lds_bytes(G.plan, rows) <= kLdsMax) G.rows = rows;
         if (!G.rows) return fail("model too large for the RNN kernel's LDS operand matrices");
-        while (G.rows > 16 && G.ntiles * (TILE / G.rows) < rnn_small_batch_blocks()) G.rows /= 2;
+        while (G.rows > 16 && G.ntiles * (TILE / G.rows) < RNN_SMALL_BATCH_BLOCKS) G.rows /= 2;
         if (h->rnn_rows && rnn_lds_bytes(G.plan, h->rnn_rows) <= kLdsMax) G.rows = h->rnn_rows;
         G.rnn_lds = rnn_lds_bytes(G.plan, G.rows);
         // models of the built-in shape class run the layer-pipelined kernel (its fixed wave roles cover 2 / 2 / 3 / 6 neuron
@@ -469,7 +452,7 @@ static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *g
             G.rnn16_lds = shape_ok && rb <= kLdsMax ? rb : 0;
             G.acts = BkActs{G.plan.dense.act, G.plan.vad.act, G.plan.noise.act, G.plan.dn.act, G.plan.out.act, G.plan.act_vo};
         }
-        G.wf = rnn_wf_enabled() && !h->rnn_rows && G.plan.dense.nb <= 2 && G.plan.vad.nb <= 2 && G.plan.noise.nb <= 3 && G.plan.dn.nb <= 6 && G.plan.vad.rec.ksteps <= WF_KS_REC &&
+        G.wf = !h->rnn_rows && G.plan.dense.nb <= 2 && G.plan.vad.nb <= 2 && G.plan.noise.nb <= 3 && G.plan.dn.nb <= 6 && G.plan.vad.rec.ksteps <= WF_KS_REC &&
                G.plan.noise.rec.ksteps <= WF_KS_REC && G.plan.dn.rec.ksteps <= WF_KS_REC && G.wf_lds <= kLdsMax;   // (k_rnn_wf's wave roles)
         tile0 += G.ntiles;
         h->md.nd = md.nd > h->md.nd ? md.nd : h->md.nd;
@@ -511,12 +494,7 @@ static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *g
         b.fault = (int *)dp;
     }
     HIPCHK(dalloc(h, &b.ticket, 1, false));
-    {
-        const char *e = dev_knob("NNN_HANDOFF_TIMEOUT_MS");
-        const long long ms = e && atoll(e) > 0 ? atoll(e) : 10000;
-        h->handoff_ticks = ms * 100000ll;   // 100 MHz
-        b.handoff_ticks = h->handoff_ticks;
-    }
+    b.handoff_ticks = HANDOFF_TICKS;
     HIPCHK(hipMalloc((void **)&h->sp_tab, 2 * 64 * sizeof(StepParams)));   // two tables: consecutive calls alternate
     h->sp_tab_cap = 64;
     // tables
@@ -1285,7 +1263,7 @@ static int back_choice(const nnn_batch *h, int g)
     return fused ? 2 : 1;
 }
 // one-frame groups of batches whose pitch launch is a single round of workgroups (two 8-wave blocks per compute unit)
-// run the LPC analysis inside k_pitch: one launch fewer on the critical path of a real-time tick (env NNN_LPC_IN_PITCH=0 / 1 forces)
+// run the LPC analysis inside k_pitch: one launch fewer on the critical path of a real-time tick
 // k_hp on two waves per tile (recurrence | everything else): for launches that leave SIMDs empty
 static bool hp_split(const nnn_batch *h)
 {
@@ -1294,8 +1272,6 @@ static bool hp_split(const nnn_batch *h)
 }
 static bool lpc_in_pitch(const nnn_batch *h, int g)
 {
-    static const int force = dev_knob("NNN_LPC_IN_PITCH") ? atoi(dev_knob("NNN_LPC_IN_PITCH")) : -1;
-    if (force >= 0) return force != 0 && g == 1;
     // (measured per one-frame call: -6 us at 4096 streams, level at 8192, +9 us at 16 384; with the sums' head start in k_hp2's launch, see
     // lpc_head: another -5 us at 4096, -6 at 8192, still +10 at 16 384)
     return g == 1 && h->S_pad <= (hp_split(h) ? 8192 : 6144) && h->lpc_wide < 0 && h->lpc_fc == 0;
@@ -1325,11 +1301,9 @@ static void launch_stage(nnn_batch *h, int s, int set0, int g, const StepParams 
         if (hp_split(h)) {
             // (a lone frame whose LPC analysis runs inside k_pitch: the part of its sums that needs none of the new frame rides along here)
             const bool head = lpc_head(h, g);
-            // groups: two tiles per block (see k_hp2).  NNN_HP_PAD_KB pads the block's LDS, e.g. past what leaves room for a k_pitch block
-            // beside it (48): measured, no gain
-            static const int pad_kb = dev_knob("NNN_HP_PAD_KB") ? atoi(dev_knob("NNN_HP_PAD_KB")) : 0;
+            // groups: two tiles per block (see k_hp2)
             if (h->hp_tpb ? h->hp_tpb == 2 : (g > 1 && NT >= 8))
-                L.go(K_HP, k_hp2<2>, dim3((NT + 1) / 2 + (head ? (5 * NT + 3) / 4 : 0)), dim3(256), (size_t)pad_kb * 1024, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0, head ? 1 : 0);
+                L.go(K_HP, k_hp2<2>, dim3((NT + 1) / 2 + (head ? (5 * NT + 3) / 4 : 0)), dim3(256), 0, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0, head ? 1 : 0);
             else
                 L.go(K_HP, k_hp2<1>, dim3(NT + (head ? (5 * NT + 1) / 2 : 0)), dim3(128), 0, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0, head ? 1 : 0);
         }
@@ -1385,17 +1359,14 @@ static void launch_stage(nnn_batch *h, int s, int set0, int g, const StepParams 
             // ... and with other batches ticking beside this one (g_call_mark) the lone frame's kernel is chosen for their sake too (k_rnn_wf holds every compute unit
             // for its five ticks: eight 4096-stream batches ticking side by side 40.2 -> 43.4 M frames/s with k_rnn, a lone batch -8 %)
             const int min_g = h->wf_min_g > 0 ? h->wf_min_g : ((G.ntiles * (TILE / WF_ROWS) >= 1024 || h->beside_others) ? 2 : 1);
-            if (G.wf && g >= min_g)
-            {
-                static const bool any_shape = dev_knob("NNN_WF_ANY") && atoi(dev_knob("NNN_WF_ANY")) != 0;   // (A/B: the run-time-plan form for every model)
-                if (G.shape_builtin && !any_shape)
+            if (G.wf && g >= min_g) {
+                if (G.shape_builtin)
                     L.go(K_RNN, k_rnn_wf<BkShapeBuiltin>, dim3((unsigned)(G.ntiles * (TILE / WF_ROWS))), dim3(64 * WF_WAVES), G.wf_lds, b, G.plan, G.wp,
                          G.wq, G.fpar, G.tile0, g);
                 else
                     L.go(K_RNN, k_rnn_wf<WfShapeAny>, dim3((unsigned)(G.ntiles * (TILE / WF_ROWS))), dim3(64 * WF_WAVES), G.wf_lds, b, G.plan, G.wp,
                          G.wq, G.fpar, G.tile0, g);
-            }
-            else
+            } else
                 L.go(K_RNN, k_rnn, dim3((unsigned)(G.ntiles * (TILE / G.rows))), dim3(64 * RNN_WAVES), G.rnn_lds, b, G.plan, G.wq, G.fpar,
                      G.tile0, G.rows, g);
         }
@@ -1491,7 +1462,7 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
     // group sizes.  A pipelined call (32 frames or more) is cut into an even number of near-equal groups of at most GROUP frames --
     // its groups alternate between two lanes, so an odd count leaves one lane a group short (three groups of 16 for the bench's
     // 48-frame call: 55.5 M frames/s at 4096 streams; two of 24: 57.2 M) -- everything else into full groups of GROUP frames, the
-    // remainder last (NNN_RAMP keeps round 2a's smaller groups at the ends of a pipelined call for comparison).
+    // remainder last (round 2a's smaller groups at the ends of a pipelined call measured 6 % slower).
     constexpr int PIPE_MIN = 32;
     // (from 16 384 streams up every kernel fills the GPU on its own and a launch beside it only costs it cache: one stream, in order,
     // unless a schedule was asked for -- 32 768 streams: 65.9 M frames/s against 64.8 with the high-pass on a stream of its own)
@@ -1503,29 +1474,17 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
     // profiles/r6_sched_sweep.txt), against one stream in order: 65 536 x 48 stages +2.6 % (lanes 2: +1.0), 65 536 x 96 lanes 2 +2.3 % (stages
     // -0.3), 32 768 x 96 lanes 2 +1.9 % (stages +0.4), 32 768 x 48 stages +1.0 % (lanes 2: -0.4): one stream per stage for calls of two
     // groups, two lanes for longer ones.  Costs the second block of scratch sets and the longer ring (650 against 360 KB per stream).
-    static const int pipe_max = dev_knob("NNN_PIPE_MAX") ? atoi(dev_knob("NNN_PIPE_MAX")) : AUTO_BIG;
-    const bool auto_big = h->sched_auto && h->S_pad > pipe_max;
+    const bool auto_big = h->sched_auto && h->S_pad > AUTO_BIG;
     const bool pipe = h->use_pipeline && h->sched != SCHED_SEQ && !h->profiling && n_frames >= PIPE_MIN && !(auto_big && h->depth < 2);
     std::vector<int> sizes;
-    if (pipe && h->ramp == 0) {
+    if (pipe) {
         int k = 2;
         while ((n_frames + k - 1) / k > h->gmax) k += 2;
         // (a batch sized for one-frame groups and an odd frame count: the even count overshoots the frames -- never an empty group)
         if (k > n_frames) k = n_frames;
         for (int i = 0; i < k; i++) sizes.push_back(n_frames / k + (i < n_frames % k ? 1 : 0));
-    }
-    for (int rem = sizes.empty() ? n_frames : 0, k = 0; rem > 0; k++) {
-        int g = h->gmax;
-        if (pipe && h->ramp == 1) {
-            g = h->gmax < k + 1 ? h->gmax : k + 1;
-            const int half = (rem + 1) / 2 > 1 ? (rem + 1) / 2 : 1;
-            if (g > half) g = half;
-        } else if (pipe && h->ramp >= 2 && k == 0) {
-            g = h->gmax / h->ramp > 0 ? h->gmax / h->ramp : 1;   // a short first group: the stages behind the high-pass start sooner
-        }
-        if (g > rem) g = rem;
-        sizes.push_back(g);
-        rem -= g;
+    } else {
+        for (int rem = n_frames; rem > 0; rem -= sizes.back()) sizes.push_back(rem < h->gmax ? rem : h->gmax);
     }
     const int n_groups = (int)sizes.size();
     const int call_sched = auto_big ? (n_groups <= 2 ? SCHED_STAGES : SCHED_LANES) : h->sched, call_lanes = auto_big ? 2 : h->n_lanes;
@@ -1543,8 +1502,7 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
     const bool early_hp = pipe && h->inputs_ready && !h->host_call && h->prev_pipe && h->prev_st == st && call_sched == SCHED_LANES && h->pool[0];
     // the per-frame parameter table: a launch of its own ahead of a pipelined call's streams; otherwise the call's first kernel (k_hp of
     // the first group) fills it on its way (a one-frame call is a handful of launches of 15-35 us: one fewer is 4 % of it)
-    static const bool fold_ok = !(dev_knob("NNN_FOLD_FILL") && atoi(dev_knob("NNN_FOLD_FILL")) == 0);   // (A/B knob)
-    const bool fold_fill = !pipe && !h->profiling && fold_ok;
+    const bool fold_fill = !pipe && !h->profiling;
     if (early_hp) {
         if (h->have_done[par]) chk(hipStreamWaitEvent(h->pool[0], h->ev_done[par], 0));   // the table's previous user (two calls back)
         hipLaunchKernelGGL(k_fill_params, dim3((n_frames + 63) / 64), dim3(64), 0, h->pool[0], tab, v0, n_frames, h->nslot);
@@ -1575,15 +1533,14 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
         // The high-pass of group k may start as soon as the ring slots it overwrites are free -- with the pitch kernel of group k - 1, and the
         // two slow each other (10.8 in HISTORY.md).  From 8192 streams up a group is long enough for the chain to wait until that pitch
         // kernel is done and still finish before group k needs it: 8192 x 48: 61.3 -> 63.9 M frames/s, 16 384: +2-3 %; at 4096 streams the
-        // window is too short (57.5 -> 56.3).  NNN_HP_AFTER = 0 | 1 | 2 | 3: never | behind pitch | fft | rnn of the previous group.
-        static const int hp_after_env = dev_knob("NNN_HP_AFTER") ? atoi(dev_knob("NNN_HP_AFTER")) : -1;
-        const int hp_after = hp_after_env >= 0 ? hp_after_env : (call_sched == SCHED_LANES && call_lanes == 1 && h->S_pad >= 8192 ? 1 : 0);
+        // window is too short (57.5 -> 56.3).
+        const bool hp_after = call_sched == SCHED_LANES && call_lanes == 1 && h->S_pad >= 8192;
         auto consumers_elsewhere = [&](int s, int k) {
             const int me = stream_of(s, k);
             if (s + 1 < ST_COUNT && stream_of(s + 1, k) != me) return true;
             if ((s == ST_HP || s == ST_PITCH || s == ST_RNN || s == ST_SYN) && k + 1 < n_groups && stream_of(s, k + 1) != me) return true;
             if (s == ST_SYN) return true;   // scratch-set / ring edges and the end of the call
-            if (hp_after > 0 && s == ST_PITCH + hp_after - 1) return true;
+            if (hp_after && s == ST_PITCH) return true;
             return false;
         };
         for (int k = 0; k < n_groups; k++) {
@@ -1603,11 +1560,10 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
                 if (s > 0) wait_for(s - 1, k);
                 if (s == ST_HP || s == ST_PITCH || s == ST_RNN || s == ST_SYN) wait_for(s, k - 1);
                 if (s == ST_PITCH) wait_for(ST_SYN, k - h->depth);
-                if (s == ST_HP && hp_after > 0) {
-                    static const int lag = dev_knob("NNN_HP_AFTER_LAG") ? atoi(dev_knob("NNN_HP_AFTER_LAG")) : 1;
-                    const int ds = ST_PITCH + hp_after - 1, pn = (int)h->prev_first.size();
-                    if (k >= lag) wait_for(ds, k - lag);
-                    else if (early_hp && pn + k - lag >= 0 && lag - k < EVR) chk(hipStreamWaitEvent(ss, h->ev[h->prev_par][ds][(pn + k - lag) % EVR], 0));
+                if (s == ST_HP && hp_after) {   // behind the previous group's pitch kernel (the previous call's last one for the first group)
+                    const int pn = (int)h->prev_first.size();
+                    if (k > 0) wait_for(ST_PITCH, k - 1);
+                    else if (early_hp && pn > 0) chk(hipStreamWaitEvent(ss, h->ev[h->prev_par][ST_PITCH][(pn - 1) % EVR], 0));
                 }
                 if (s == ST_HP) {
                     // slots written now held frames (newest of this group) - nslot and older; their last readers are the
@@ -1769,10 +1725,9 @@ static int process_host_span_impl(nnn_batch *h, const void *in, void *out, float
     // Small calls -- the RNNoise C ABI's state is a batch of one, a frame per call -- have nothing to overlap and pay for every runtime call they
     // make: two or three staged copies of a few kilobytes cost more than the three kernels between them.  Up to ZC_MAX bytes the kernels work on
     // page-locked host memory directly (the input read over the link by the first kernel, audio and VAD written over it by the last): one
-    // memcpy in, one wait, one memcpy out.  Same kernels, same bits.
+    // memcpy in, one wait, one memcpy out.  Same kernels, same bits.  An explicit NNN_HOST_CHUNK always takes the staged path below.
     constexpr size_t ZC_MAX = (size_t)1 << 20;
-    static const bool zc_on = !(dev_knob("NNN_ZERO_COPY") && atoi(dev_knob("NNN_ZERO_COPY")) == 0);   // (A/B knob)
-    if (zc_on && span + vbytes + 16 <= ZC_MAX) {
+    if (h->host_chunk < 0 && span + vbytes + 16 <= ZC_MAX) {
         const size_t vofs = (span + 15) / 16 * 16;
         if (!h->zc_host) {
             NNN_RT_LOCK;
@@ -2075,7 +2030,7 @@ extern "C" int nnn_batch_debug_withhold_flag(nnn_batch *h, int frames_ahead)
     const int seq = frames_ahead < 0 ? 0 : (int)((h->frame_count + (uint64_t)frames_ahead) & 0x3fffffffu) + 1;
     for (int set = 0; set < h->nset; set++) {
         h->b[set].dbg_withhold = seq;
-        h->b[set].handoff_ticks = seq ? 20000000ll : h->handoff_ticks;   // the withheld flag is given up on after 0.2 s
+        h->b[set].handoff_ticks = seq ? 20000000ll : HANDOFF_TICKS;   // the withheld flag is given up on after 0.2 s
     }
     return 0;
 }

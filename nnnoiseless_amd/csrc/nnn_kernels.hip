@@ -35,10 +35,7 @@ namespace nnn {
 // and written back from, as many L2s.  Tile t goes to XCD t mod 8 instead: where k_hp's block t and k_pitch's blocks of tile t ran.
 __device__ __forceinline__ void xcd_tile_block(int blk, int ntiles, int bpt, int &tile, int &sub)
 {
-    int m8 = ntiles & ~7;   // the tiles that come in eights are dealt to the XCDs; the last few keep block order
-#ifdef NNN_NO_XCD_MAP
-    m8 = 0;
-#endif
+    const int m8 = ntiles & ~7;   // the tiles that come in eights are dealt to the XCDs; the last few keep block order
     if (blk < m8 * bpt) {
         const int xcd = blk & 7, j = blk >> 3;
         tile = xcd + 8 * (j / bpt);
@@ -53,10 +50,7 @@ __device__ __forceinline__ void xcd_tile_block(int blk, int ntiles, int bpt, int
 // blocks of its XCD: blk -> (unit, tile, sub)
 __device__ __forceinline__ void xcd_tile_block_units(int blk, int ntiles, int bpt, int n, int &unit, int &tile, int &sub)
 {
-    int m8 = ntiles & ~7;
-#ifdef NNN_NO_XCD_MAP
-    m8 = 0;
-#endif
+    const int m8 = ntiles & ~7;
     if (blk < m8 * bpt * n) {
         const int xcd = blk & 7, j = blk >> 3, tb = j / n;
         unit = j - tb * n;
@@ -1264,24 +1258,6 @@ static_assert(PK_SEG_F1 % 2 == 0 && PK_SEG_F1 <= PK_FINE_K, "");
 // (defined behind the transforms, further down: the X transform of a one-frame call in rider blocks of k_pitch's launch)
 __device__ __forceinline__ void xt_rider(const Buffers &b, const StepParams *sp, int rb, void *lds);
 
-#ifndef NNN_BISECT_A
-#define NNN_BISECT_A 0
-#endif
-#ifndef NNN_BISECT_B
-#define NNN_BISECT_B 0
-#endif
-#ifndef NNN_BISECT_C
-#define NNN_BISECT_C 0
-#endif
-#ifndef NNN_BISECT_D
-#define NNN_BISECT_D 0
-#endif
-#ifndef NNN_PK_PRIO
-#define NNN_PK_PRIO 0
-#endif
-#ifndef NNN_PK_LATE_WINDOW
-#define NNN_PK_LATE_WINDOW 1
-#endif
 #ifndef NNN_PK_MINWAVES
 #define NNN_PK_MINWAVES 4   // waves per SIMD: two blocks of 8 waves per CU, <= 128 registers
 #endif
@@ -1446,9 +1422,6 @@ __global__ void __launch_bounds__(PK_T, NNN_PK_MINWAVES) k_pitch(Buffers b, cons
             }
             if (tid < PK_SPB * 5 + 2) (&L.u.a.mask[0][0])[tid] = 0u;   // the survivors' masks, count and the full-search flag
         }
-#if !NNN_PK_LATE_WINDOW
-        if (f + 1 < f_end) pk_window_load(b, sp0 + f + 1, tile, q0, tid, win, fir);   // the next frame's window travels behind this frame's work
-#endif
         __syncthreads();
         NNN_STAMP(b, 4);
         // ---- coarse search (ref: src/pitch.rs:83-84 -> :296-363, :372-405).  find_best_pitch returns the two lags with the largest
@@ -1783,7 +1756,6 @@ __global__ void __launch_bounds__(PK_T, NNN_PK_MINWAVES) k_pitch(Buffers b, cons
                 }
             }
         }
-        if (NNN_PK_PRIO && wv >= 5) wave_prio<0>();
         if (full) {
             if (wv == 5) chain_y = pk_chain_fine(pcs, cq, cs, chain_y, PK_SEG_F1, PK_FINE_K, L.ckf);
             if (dec_lane) {
@@ -2006,10 +1978,10 @@ __global__ void __launch_bounds__(PK_T, NNN_PK_MINWAVES) k_pitch(Buffers b, cons
 #pragma unroll
             for (int c = 0; c < 3; c++) L.u.f.part[wave + 8 * c][qi][s] = acc[c];
         }
-#if NNN_PK_LATE_WINDOW   // the next frame's window is requested here, behind the candidates' inner products (round 6; round 5: ahead of them; until then behind the FIR): its 32 registers are free
-                        // through the cross-correlation and the searches, and the ~8 us left of the frame still cover the trip (k_pitch -2.6 %; 0 = as before)
+        // the next frame's window is requested here, behind the candidates' inner products (round 6; round 5: ahead of them; until then behind
+        // the FIR): its 32 registers are free through the cross-correlation and the searches, and the ~8 us left of the frame still cover the
+        // trip (k_pitch -2.6 %)
         pk_window_load(b, sp0 + f + 1, tile, q0, f + 1 < f_end ? tid : PK_T, win, fir);   // (the group's last frame: nothing to load, and no old value kept)
-#endif
         if (dec_lane) {
             if (chain && f > 0) {
                 // the previous frame of these streams is another workgroup's: wait for its flag, then take its pitch and gain
@@ -2142,13 +2114,7 @@ __global__ void __launch_bounds__(PK_T, NNN_PK_MINWAVES) k_pitch(Buffers b, cons
 // time, profiles/r3_experiments_ab.txt block A).  Round 4 took that back: the same source then rounds the same way in every kernel
 // it is inlined into, and the fused back end (k_back) -- the same transforms and synthesis inside another kernel, where the
 // compiler's choices came out differently in a third of the spectrum's bins -- gives the bits of k_fft_xp / k_synth, so a stream
-// may change back end from call to call.  NNN_FFT_CONTRACT=1 builds the freely fusing variant for A/B runs.
-#ifndef NNN_FFT_CONTRACT
-#define NNN_FFT_CONTRACT 0
-#endif
-#if NNN_FFT_CONTRACT
-#pragma clang fp contract(fast)
-#endif
+// may change back end from call to call.
 constexpr int NFFT = 480;
 
 __device__ __forceinline__ float2 cmulf(float2 a, float2 w)
@@ -2248,14 +2214,11 @@ constexpr int FFT_SPB = 4;
 // per-lane constant.  k_fft_xp 19.6 -> 18.9 us per frame at 4096 streams, 325 -> 321 at 65536 (same box).
 __device__ __forceinline__ int bsk(int k) { return k + (k >> 3); }
 constexpr int BSK_LEN = 400 + 400 / 8;
-// NNN_FFT_LANE_TW=1 (on since round 5; 0 builds the variant without): the second and third pass's twiddles as the lanes use them -- a
+// Lane twiddles (since round 5): the second and third pass's twiddles as the lanes use them -- a
 // lane's twiddles are constants of the lane, one LDS read each instead of index, wrap and sign (five vector instructions a piece) -- in
 // k_synth, whose blocks copy the tables once per group of frames (-6.6 % vector instructions, -1.5 % time: profiles/r4_experiments_ab.txt M,
 // profiles/r5_experiments_ab.txt C); the kernels whose blocks copy the tables per stream-frame keep the half circle and copy the part of
 // the image before these tables only.  Same products of the same factors: bit-identical to the variant without.
-#ifndef NNN_FFT_LANE_TW
-#define NNN_FFT_LANE_TW 1
-#endif
 constexpr int FFT_TW2 = 2 * 5 * 64, FFT_TW3 = 9 * 64;
 struct alignas(16) FftLds {
     float2 tw[NFFT];           // exp(-2 pi i k / 960), k < 480; the other half of the circle is the negation
@@ -2266,17 +2229,11 @@ struct alignas(16) FftLds {
     float dct[NB * NB];        // DCT table (ref: src/lib.rs:118-127): the feature head's two transforms read 44 of its rows per stream-frame
                                // (from global memory they were half of k_fft_xp's vector-memory instructions; same time either way)
     float pad_[2];
-#if NNN_FFT_LANE_TW
     float2 tw2[FFT_TW2];       // fft_pass<6, 8>: [it][r - 1][lane]; copied only by the kernels that use them (fft_tables_load)
     float2 tw3[FFT_TW3];       // fft_pass<10, 48>: [r - 1][lane]
-#endif
 };
 static_assert(sizeof(FftLds) % 16 == 0, "copied as 16-byte pieces");
-#if NNN_FFT_LANE_TW
 constexpr int FFT_TABLES_SHORT = (int)offsetof(FftLds, tw2);
-#else
-constexpr int FFT_TABLES_SHORT = (int)sizeof(FftLds);
-#endif
 static_assert(FFT_TABLES_SHORT % 16 == 0, "");
 // Fills the block's tables from the image the host built in exactly this layout (Buffers::fft_img): a straight copy of 16-byte
 // pieces.  (Building them in the kernel from the plain tables -- skewed index, byte and short conversions, scattered narrow LDS
@@ -2311,14 +2268,12 @@ __host__ inline void fft_tables_image(FftLds &t, const float2 *tw960, const floa
     memset(&t, 0, sizeof(t));
     for (int i = 0; i < NB * NB; i++) t.dct[i] = dct[i];
     for (int i = 0; i < NFFT; i++) t.tw[i] = tw960[i];
-#if NNN_FFT_LANE_TW
     auto at = [&](int k) { const float2 w = tw960[k >= NFFT ? k - NFFT : k]; return k >= NFFT ? make_float2(-w.x, -w.y) : w; };   // tw960_at
     for (int it = 0; it < 2; it++)       // fft_pass<6, 8>: butterfly j = lane + 64 it < 80, k = j % 8, twiddle (r k 20) % 960
         for (int r = 1; r < 6; r++)
             for (int l = 0; l < 64; l++) t.tw2[(it * 5 + r - 1) * 64 + l] = at((r * ((l + 64 * it) % 8) * 20) % 960);
     for (int r = 1; r < 10; r++)         // fft_pass<10, 48>: butterfly j = lane < 48, k = j, twiddle (r k 2) % 960
         for (int l = 0; l < 64; l++) t.tw3[(r - 1) * 64 + l] = at((r * (l % 48) * 2) % 960);
-#endif
     for (int i = 0; i < 400; i++) {
         t.frac[i + (i >> 3)] = bin_frac[i];
         t.band[i] = (unsigned char)bin_band[i];
@@ -2406,7 +2361,6 @@ __device__ __forceinline__ void fft480_regs(float2 (&v)[8], float2 *buf, const f
     }
     wave_lds_sync();
     if (RL) lane = launder_v(lane);
-#if NNN_FFT_LANE_TW
     if (LT) {   // (tw = FftLds::tw of a block that copied the whole image)
         const float2 *tw2 = (const float2 *)((const char *)tw + (offsetof(FftLds, tw2) - offsetof(FftLds, tw)));
         fft_pass<6, 8, true, false, true>(buf, tw2, lane);
@@ -2414,7 +2368,6 @@ __device__ __forceinline__ void fft480_regs(float2 (&v)[8], float2 *buf, const f
         fft_pass<10, 48, false, false, true>(buf, tw2 + FFT_TW2, lane);
         return;
     }
-#endif
     fft_pass<6, 8, true, false>(buf, tw, lane);
     if (RL) lane = launder_v(lane);
     fft_pass<10, 48, false, false>(buf, tw, lane);
@@ -2644,19 +2597,12 @@ __device__ __forceinline__ void transform_inputs(const Buffers &b, const StepPar
     // the wave's critical path per stream-frame (these kernels move enough bytes for that to show)
     SamplePair sx[8], spw[8];
     if (!XR) window_load(h, ring, rb, 0, lane, sx);
-#ifndef NNN_FFT_LATE_P   // (A/B knob: the second window requested where its transform starts, as before)
     if (WITH_P && !FUSED) window_load(h, ring, rb, lag, lane, spw);   // (fused: sixteen registers it has not got; requested after the first transform)
-#endif
     float2 X[8];
     float2 *dx = b.X + (size_t)s * FSTR;
     if (XR) spectrum_load(dx, X, lane);
     else window_rfft<FUSED>(b, sx, w, t, Z, X, lane, !FUSED);
-    // NNN_PROBE_XP (developer probe, wrong audio, timing only): the spectra are not stored here and k_synth reads them from a
-    // region small enough to stay in the XCD's L2 -- an upper bound on what keeping X and P on chip between the transforms
-    // and the synthesis (a fused back end) could gain from the removed HBM round trip.
-#ifndef NNN_PROBE_XP
     if (!XR && (!FUSED || b.taps)) spectrum_store(dx, X, lane);   // (fused: the spectra stay in registers; memory sees them for the parity taps only)
-#endif
     NNN_FUSED_RELAUNDER();
     float *vv = (float *)Z, *vc = vv + BSK_LEN;   // per-bin quantities of the band sums, skewed (bsk)
     float exv;
@@ -2679,20 +2625,14 @@ __device__ __forceinline__ void transform_inputs(const Buffers &b, const StepPar
     wave_lds_sync();
     NNN_FUSED_RELAUNDER();
     float2 Y[8];
-#ifdef NNN_FFT_LATE_P
-    window_load(h, ring, rb, lag, lane, spw);
-#else
     if (FUSED) window_load(b.hist + (size_t)__builtin_amdgcn_readfirstlane(s) * hist_stride(b.nslot), ring, rb, lag, lane, spw);
-#endif
     if (FUSED) {   // (the window again, from the L2: sixteen registers less across the first transform and the band sums of a wave that has 128)
 #pragma unroll
         for (int r = 0; r < 8; r++) w[r] = ((const float2 *)b.window_a)[(lane < FFT_P1 ? lane : FFT_P1 - 1) + FFT_P1 * r];
     }
     window_rfft<FUSED>(b, spw, w, t, Z, Y, lane, false);
     float2 *dp = b.P + (size_t)s * FSTR;
-#ifndef NNN_PROBE_XP
     if (!FUSED || b.taps) spectrum_store_p(dp, Y, lane, b.taps != 0);
-#endif
 #pragma unroll
     for (int u = 0; u < 8; u++) {
         const int k = rfft_slot_bin(lane, u);
@@ -3092,13 +3032,9 @@ __device__ __forceinline__ float load_split(const unsigned short *P, int plane_s
     return (bf16_f32(P[idx]) + bf16_f32(P[idx + plane_stride])) + bf16_f32(P[idx + 2 * plane_stride]);
 }
 
-// NNN_RNN_GEMM_PLANES = 2 (developer probe): the products use the hi and mid planes only -- activations truncated to 16
-// significand bits -- while the planes are stored and the states kept as before: what dropping a third of the MFMAs and operand reads is
-// worth, and what 16-bit activations do to gains and VAD, before anything is rebuilt around two planes.
-#ifndef NNN_RNN_GEMM_PLANES
-#define NNN_RNN_GEMM_PLANES 3
-#endif
-constexpr int GPL = NNN_RNN_GEMM_PLANES;
+// operand planes in the products: all three (two -- activations truncated to 16 significand bits -- were measured in round 4,
+// profiles/r4_experiments_ab.txt B)
+constexpr int GPL = 3;
 // Weight fragments of one GEMM group: all k-steps (up to KSMAX) are requested together so that a layer pays
 // one trip to the Infinity Cache / HBM instead of one per k-step.
 constexpr int KSMAX = 4;
@@ -3997,9 +3933,6 @@ __global__ void __launch_bounds__(64 * WF_WAVES, NNN_WF_MINWAVES) k_rnn_wf(Buffe
     NNN_STAMP(b, 52);
 }
 
-#if NNN_FFT_CONTRACT
-#pragma clang fp contract(fast)   // (k_synth: downstream of the transforms, see the note above them)
-#endif
 // interpolated band gain at bin k (ref: src/lib.rs:84-97): zero for k >= 400
 __device__ __forceinline__ float interp_gain(const float *g, int k, const float *bin_frac, const unsigned char *bin_band)
 {
@@ -4160,7 +4093,7 @@ __device__ __forceinline__ void synth_frame(const Buffers &b, const StepParams *
         wlo[u] = on ? ((const float4 *)b.window_s)[n] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // (window / 2: the inverse transform's halving rides on it)
         whi[u] = on ? ((const float4 *)b.window_s)[FRAME / 4 + n] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
-    fft480_regs<true, NNN_FFT_LANE_TW && !SMV_IO>(zin, A, t.tw, lane);   // time samples: x[2n] = A[n].y, x[2n+1] = A[n].x
+    fft480_regs<true, !SMV_IO>(zin, A, t.tw, lane);   // time samples: x[2n] = A[n].y, x[2n+1] = A[n].x
     if (lane == 0 && vad_out && s < b.S) vad_out[s] = vadv;
     const bool quad_ok = ch == 1 && (((size_t)o) & (size_t)(4 * elem - 1)) == 0;
 #pragma unroll
@@ -4208,7 +4141,7 @@ __global__ void __launch_bounds__(64 * FFT_SPB, NNN_SYN_MINWAVES) k_synth(Buffer
     if (tile * TILE + sub * FFT_SPB >= b.S) return;   // (a block whose streams are all padding -- the last tile of a batch that is not a multiple of 64 -- has nothing to do)
     const int lane0 = threadIdx.x & 63, sl = sub * FFT_SPB + wave, s = tile * TILE + sl;
     int lane = lane0;
-    fft_tables_load(t, b, NNN_FFT_LANE_TW != 0);
+    fft_tables_load(t, b, true);
     float *sm = b.synth_mem + (size_t)s * FRAME;
     float4 smq[2];   // overlap memory as sample quads, carried from frame to frame in registers
 #pragma unroll
@@ -4225,11 +4158,7 @@ __global__ void __launch_bounds__(64 * FFT_SPB, NNN_SYN_MINWAVES) k_synth(Buffer
     for (int f = 0; f < g; f++) {
         lane = launder_v(lane0);   // keep the frame loop's addresses inside the loop (see launder_v)
         const size_t fo = (size_t)b.S_pad * (size_t)f;   // this frame's scratch set
-#ifdef NNN_PROBE_XP
-        const float2 *Xg = b.X + (size_t)(s & 255) * FSTR, *Pg = b.P + (size_t)(s & 255) * FSTR;
-#else
         const float2 *Xg = b.X + (fo + s) * FSTR, *Pg = b.P + (fo + s) * FSTR;
-#endif
         // every global load of this frame is independent of its own results: issue them all now.  The spectra arrive as the
         // transforms held them, (bin k, bin 480 - k) pairs in 16-byte loads (spectrum_load)
         const bool live = NNN_TIF(b, silence, 1, f, tile, sl)[0] == 0;

@@ -123,7 +123,6 @@ template <class T> __device__ __forceinline__ void st_global(void *p, T v)
 // from the value loop-variant for the compiler: otherwise every address of every phase is hoisted out of the frame loop as
 // loop invariant, hundreds of registers wide, and spilled (measured: 300 spills in k_rnn without it, none with it).
 __device__ __forceinline__ void wf_setprio_high() { __builtin_amdgcn_s_setprio(3); }
-template <int P> __device__ __forceinline__ void wave_prio() { __builtin_amdgcn_s_setprio(P); }   // issue priority of the calling wave (0 .. 3)
 __device__ __forceinline__ int launder_v(int x)
 {
     asm volatile("" : "+v"(x));
@@ -145,12 +144,6 @@ __device__ __forceinline__ int launder_s(int x)
 // like v_mul_f32 / v_add_f32.
 typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2f mk2(float x, float y) { v2f r = {x, y}; return r; }
-__device__ __forceinline__ float smul(float a, float b)
-{
-    float r;
-    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 // a single add that stays a single add (sequential sums of packed products: the compiler's pairing across accumulators
 // would cost register moves)
 __device__ __forceinline__ float sadd(float a, float b)
@@ -159,17 +152,6 @@ __device__ __forceinline__ float sadd(float a, float b)
     asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-#ifndef NNN_NO_PK
-#define NNN_NO_PK 0
-#endif
-#if NNN_NO_PK   // experiment (round 6): every packed helper as two plain instructions -- same roundings, half-rate issue slots each
-__device__ __forceinline__ v2f pk_mul(v2f a, v2f b) { return mk2(smul(a.x, b.x), smul(a.y, b.y)); }
-__device__ __forceinline__ v2f pk_mul_bx(v2f a, v2f b) { return mk2(smul(a.x, b.x), smul(a.x, b.y)); }
-__device__ __forceinline__ v2f pk_mul_by(v2f a, v2f b) { return mk2(smul(a.y, b.x), smul(a.y, b.y)); }
-__device__ __forceinline__ v2f pk_add(v2f a, v2f b) { return mk2(sadd(a.x, b.x), sadd(a.y, b.y)); }
-__device__ __forceinline__ v2f pk_add_bx(v2f a, v2f b) { return mk2(sadd(a.x, b.x), sadd(a.y, b.x)); }
-__device__ __forceinline__ v2f pk_add_by(v2f a, v2f b) { return mk2(sadd(a.x, b.y), sadd(a.y, b.y)); }
-#else
 __device__ __forceinline__ v2f pk_mul(v2f a, v2f b)       // (a.x b.x, a.y b.y)
 {
     v2f r;
@@ -206,7 +188,6 @@ __device__ __forceinline__ v2f pk_add_by(v2f a, v2f b)    // (a.x + b.y, a.y + b
     asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-#endif
 
 // ---- the certified coarse pitch search's primitives (k_pitch, round 6) ----
 // (a, b) rounded to nearest-even bf16, a in the low half: one v_cvt_pk_bf16_f32

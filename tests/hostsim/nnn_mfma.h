@@ -150,7 +150,6 @@ static inline uint4 ld_global_u4(const void *p) { return ld_global<uint4>(p); }
 template <class T> static inline void st_global(void *p, T v) { memcpy(p, &v, sizeof(T)); }
 
 static inline void wf_setprio_high() {}
-template <int P> static inline void wave_prio() {}
 static inline int launder_v(int x) { return x; }
 static inline int launder_s(int x) { return x; }
 static inline void keep_v(float) {}
@@ -167,7 +166,6 @@ static inline v2f pk_add(v2f a, v2f b) { return mk2(a.x + b.x, a.y + b.y); }
 static inline v2f pk_add_bx(v2f a, v2f b) { return mk2(a.x + b.x, a.y + b.x); }
 static inline v2f pk_add_by(v2f a, v2f b) { return mk2(a.x + b.y, a.y + b.y); }
 static inline float sadd(float a, float b) { return a + b; }
-static inline float smul(float a, float b) { return a * b; }
 
 // ---- the certified coarse pitch search's primitives ----
 static inline unsigned short bf16_rn_bits(float f)

@@ -74,23 +74,28 @@ def test_denoise_signal(hostsim_lib, oracle_mod, weights_bytes):
 
 def test_host_calls_in_chunks_are_bit_identical(hostsim_lib, monkeypatch):
     """A long host-buffer call crosses the bus in chunks of frames (include/nnn_batch.h nnn_batch_process_host); the chunks must
-    not show: planar f32, and packed int16 stereo with the dropped first frame (outputs one frame ahead of their inputs)."""
+    not show: planar f32, and packed int16 stereo with the dropped first frame (outputs one frame ahead of their inputs).  The staged
+    calls, in one piece and in chunks, give the zero-copy path's bits."""
     import nnnoiseless_amd as nn
     from nnnoiseless_amd import _ffi
     pcm = _speech(7, 4)
     planar = np.ascontiguousarray(pcm.T.reshape(4, 7, 480).astype(np.float32))
     inter = np.ascontiguousarray(pcm.reshape(-1, 2, 2).transpose(1, 0, 2))   # 2 groups x 2 channels
     res = {}
-    for chunk in ("0", "1", "2", "3"):      # (1: what the default picks for short calls on large batches since round 5)
-        monkeypatch.setenv("NNN_HOST_CHUNK", chunk)
+    # None: the variable unset, a call this small takes the zero-copy path; set, every call is staged ("0": in one piece)
+    for chunk in (None, "0", "1", "2", "3"):      # (1: what the default picks for short calls on large batches since round 5)
+        if chunk is None:
+            monkeypatch.delenv("NNN_HOST_CHUNK", raising=False)
+        else:
+            monkeypatch.setenv("NNN_HOST_CHUNK", chunk)
         bd = nn.BatchDenoiser(4, lib=hostsim_lib)
         a, va = bd.process(planar)
         bd.reset()
         b, vb = bd.process_pcm(inter, _ffi.PCM_I16, 2, discard_first=True)
         assert b.shape == (2, 6 * 480, 2)
         res[chunk] = (a, va, b, vb)
-    for chunk in ("1", "2", "3"):
-        for u, v in zip(res["0"], res[chunk]):
+    for chunk in ("0", "1", "2", "3"):
+        for u, v in zip(res[None], res[chunk]):
             assert np.array_equal(u, v), chunk
 
 
