@@ -106,8 +106,82 @@ enum Stage { ST_HP, ST_PITCH, ST_FFT, ST_RNN, ST_SYN, ST_COUNT };
 constexpr int NSTREAMS = 5;    // internal streams of a pipelined call
 constexpr int EVR = 16;        // event ring: groups of one call that may still be referred to
 enum SchedMode { SCHED_SEQ = 0, SCHED_LANES = 1, SCHED_STAGES = 2 };
-constexpr int AUTO_BIG = 16384;   // streams above which the automatic schedule changes (process_frames)
+constexpr int AUTO_BIG = 16384;   // streams above which the automatic schedule changes (plan_call)
 constexpr long long HANDOFF_TICKS = 10000ll * 100000ll;   // Buffers::handoff_ticks outside the test hook: 10 s of the 100 MHz clock
+
+// Every setting that picks a kernel or a schedule.  read_paths fills it from the environment at batch creation; the setters change
+// back_mode, use_pipeline, inputs_ready and (nnn_batch_set_schedule) sched, n_lanes and sched_auto later.  Only creation, the two plan
+// functions (plan_call, plan_group) and the host-buffer chunk rules read it.
+struct Paths {
+    int sched = SCHED_LANES;       // how a multi-frame call spreads over streams (env NNN_SCHED: seq | lanes | stages)
+    bool sched_auto = true;        // nobody chose a schedule (NNN_SCHED / NNN_LANES / nnn_batch_set_schedule): the rule of plan_call
+    int n_lanes = 1;               // SCHED_LANES: lanes (the caller's stream + internal ones) besides the high-pass stream; env NNN_LANES, 1..4.
+                                   // One since the end of round 3: with the frames of a group side by side in every kernel a second group in flight
+                                   // only gets in the first one's way (4096 streams: 55.5 against 54.8 M frames/s, 16 384: 63.8 / 62.3; profiles AN)
+                                   // (measured at 4096 streams x 48 frames: 1: 28.5, 2: 37.1, 3: 32.9, 4: 32.2 M frames/s -- the default 4 hardware
+                                   // queues are shared with the host's own streams)
+    int host_chunk = -1;           // frames per chunk of a host-buffer call (env NNN_HOST_CHUNK): -1 = by call length and size (small
+                                   // calls zero-copy), 0 = the whole call in one piece; set, it always takes the staged path
+    int wf_min_g = 0;              // groups shorter than this run k_rnn instead of the layer-pipelined kernel (env NNN_RNN_WF_MIN_G; 0 = by batch size)
+    int rnn_rows = 0;              // forced rows per RNN block (env NNN_RNN_ROWS), 0 = by model size and batch size
+    int hp_split = -1;             // k_hp on two waves per tile (k_hp2): -1 = for launches of up to 256 tiles, 0 / 1 = never / always (env NNN_HP_SPLIT)
+    int lpc_head = -1;             // one-frame calls: the LPC sums' first 608 steps in k_hp2's launch (0 = never; env NNN_LPC_HEAD)
+    int pitch_chain = 1;           // k_pitch: one workgroup per (frame, quarter tile) instead of a frame loop: 1 = below 16384 streams, 0 = never, 2 = always (env NNN_PITCH_CHAIN)
+    int hp_tpb = 0;                // k_hp2's tiles per block: 0 = by launch (2 for groups, 1 for lone frames), 1 / 2 forced (env NNN_HP_TPB)
+    int x_rides = -1;              // one-frame calls: the fused back end's X transform in rider blocks of k_pitch's launch (-1 = up to 8192 streams; env NNN_X_RIDES)
+    int lpc_wide = -1;             // k_lpc_wide (one lag per wave): -1 = for launches below 512 waves, 0 / 1 = never / always (env NNN_LPC_WIDE)
+    int lpc_fc = 0;                // k_lpc: frames per wave, 0 = by launch size (env NNN_LPC_FC)
+    int back_mode = -1;            // the fused back end (k_back, nnn_back.hip): 0 = never, 1 = one-frame groups (the real-time tick), 2 = every group;
+                                   // 3 / 4 = its RNN stretch alone (k_back<false>) in place of k_rnn / k_rnn_wf for one-frame / all groups;
+                                   // -1 = by measurement (plan_group): one-frame groups only, fused up to 8192 streams, the RNN stretch
+                                   // alone above that or with other batches ticking beside this one (nnn_batch_set_back_end)
+    bool use_pipeline = true;      // nnn_batch_set_pipeline
+    bool inputs_ready = false;     // the caller's promise that a call's input is final when the call is made (nnn_batch_set_inputs_ready)
+};
+static Paths read_paths()
+{
+    Paths p;
+    if (const char *e = knob("NNN_HOST_CHUNK")) p.host_chunk = atoi(e);
+    if (const char *e = knob("NNN_RNN_WF_MIN_G")) p.wf_min_g = atoi(e);
+    if (const char *e = knob("NNN_HP_SPLIT")) p.hp_split = atoi(e);
+    if (const char *e = dev_knob("NNN_HP_TPB")) p.hp_tpb = atoi(e);
+    if (const char *e = knob("NNN_LPC_HEAD")) p.lpc_head = atoi(e);
+    if (const char *e = dev_knob("NNN_X_RIDES")) p.x_rides = atoi(e);
+    if (const char *e = knob("NNN_PITCH_CHAIN")) p.pitch_chain = atoi(e);
+    if (const char *e = dev_knob("NNN_LPC_WIDE")) p.lpc_wide = atoi(e);
+    if (const char *e = dev_knob("NNN_LPC_FC")) p.lpc_fc = atoi(e);
+    if (const char *e = knob("NNN_SCHED")) {
+        if (!strcmp(e, "seq")) p.sched = SCHED_SEQ;
+        else if (!strcmp(e, "lanes")) p.sched = SCHED_LANES;
+        else if (!strcmp(e, "stages")) p.sched = SCHED_STAGES;
+        p.sched_auto = false;
+    }
+    if (const char *e = knob("NNN_LANES")) {
+        const int v = atoi(e);
+        if (v >= 1 && v <= NSTREAMS - 1) p.n_lanes = v;
+        p.sched_auto = false;
+    }
+    if (const char *e = knob("NNN_RNN_ROWS")) {
+        const int v = atoi(e);
+        if (v == 16 || v == 32) p.rnn_rows = v;
+    }
+    return p;
+}
+
+// What one group of frames runs (plan_group; launch_stage dispatches on it)
+enum BackEnd { BACK_UNFUSED = 0, BACK_RNN_ALONE = 1, BACK_FUSED = 2 };   // k_fft_xp -> RNN -> k_synth, the same with k_back<false> as the RNN, k_back<true>
+enum RnnKernel : uint8_t { RK_BACK, RK_WF_BUILTIN, RK_WF_ANY, RK_PLAIN };   // k_back<false>, k_rnn_wf<BkShapeBuiltin>, k_rnn_wf<WfShapeAny>, k_rnn
+struct GroupPlan {
+    int g = 0;                     // frames
+    BackEnd back = BACK_UNFUSED;
+    int hp = 0;                    // 0 = k_hp, 1 / 2 = k_hp2<1> / k_hp2<2>
+    bool head = false;             // k_hp2 also runs the LPC sums' head (and k_pitch<true> takes it)
+    bool lpc_in_pitch = false;     // k_pitch<true> does the LPC analysis
+    int lpc_fc = 0;                // otherwise: k_lpc with lpc_fc frames per wave behind the high-pass, 0 = k_lpc_wide (lpc_launch)
+    bool chain = false;            // k_pitch's frames side by side, chained through flags
+    bool riders = false;           // the fused back end's X transform in rider blocks of k_pitch's launch
+    uint8_t *rnn = nullptr;        // RnnKernel of each resident model group (made at creation)
+};
 
 struct nnn_batch {
     Buffers b[NSET];               // same state, NSET scratch sets (views into one allocation per scratch array: set s lies
@@ -127,15 +201,9 @@ struct nnn_batch {
         size_t back_lds = 0, rnn16_lds = 0;   // dynamic LDS of k_back<true> / k_back<false>; 0 = the model is outside the kernel's shape class
         BkActs acts = {};
     };
-    int x_rides = -1;              // one-frame calls: the fused back end's X transform in rider blocks of k_pitch's launch (-1 = up to 8192 streams; env NNN_X_RIDES)
-    int lpc_head = -1;             // one-frame calls: the LPC sums' first 608 steps in k_hp2's launch (0 = never; env NNN_LPC_HEAD, read at creation)
-    int hp_tpb = 0;                // k_hp2's tiles per block: 0 = by launch (2 for groups, 1 for lone frames), 1 / 2 forced (env NNN_HP_TPB, read at creation)
-    int hp_split = -1;             // k_hp on two waves per tile (k_hp2): -1 = for launches of up to 256 tiles, 0 / 1 = never / always (env NNN_HP_SPLIT, read at creation)
-    int back_mode = -1;            // the fused back end (k_back, nnn_back.hip): 0 = never, 1 = one-frame groups (the real-time tick), 2 = every group;
-                                   // 3 / 4 = its RNN stretch alone (k_back<false>) in place of k_rnn / k_rnn_wf for one-frame / all groups;
-                                   // -1 = by measurement (back_choice): one-frame groups only, fused up to 8192 streams, the RNN stretch
-                                   // alone above that or with other batches ticking beside this one (nnn_batch_set_back_end)
-    int rnn_rows = 0;              // forced rows per RNN block (env NNN_RNN_ROWS), 0 = by model size and batch size
+    Paths paths;                   // as of now
+    Paths created;                 // as the batch was created with (clone: depth, rows and kernel forms follow from it)
+    GroupPlan plan;                // the group being enqueued
     std::vector<ModelGroup> groups;
     std::vector<RNNModel> models;  // host copies of the resident models (clone)
     std::vector<int> group_streams;
@@ -160,9 +228,6 @@ struct nnn_batch {
     size_t zc_cap = 0;
     hipStream_t copy_in = nullptr, copy_out = nullptr;   // host-buffer calls in chunks: uploads, downloads (created on first use)
     std::vector<hipEvent_t> ev_up, ev_run;               // per chunk: uploaded, processed
-    int wf_min_g = 0;               // groups shorter than this run k_rnn instead of the layer-pipelined kernel (env NNN_RNN_WF_MIN_G; 0 = by batch size)
-    int host_chunk = -1;            // frames per chunk of a host-buffer call (env NNN_HOST_CHUNK): -1 = by call length and size (small
-                                    // calls zero-copy), 0 = the whole call in one piece; set, it always takes the staged path
     StepParams *sp_tab = nullptr;   // device, per-frame parameter table of a call
     int sp_tab_cap = 0;
     hipStream_t stream = nullptr;   // default launch stream
@@ -178,13 +243,10 @@ struct nnn_batch {
     uint64_t prev_frame0 = 0;
     int prev_par = 0;
     std::vector<int> prev_first;
-    bool inputs_ready = false;      // the caller's promise that a call's input is final when the call is made
     volatile int *fault_host = nullptr;   // host view of Buffers::fault (page-locked, mapped): a hand-off that never arrived
     unsigned tickets = 0;           // work items handed out so far by chained k_pitch launches (Buffers::ticket never restarts)
     unsigned *frame_log = nullptr;  // nnn_batch_set_frame_log: the next frame's record (device), and the frames that still have room
     size_t frame_log_left = 0;
-    int lpc_fc = 0;                 // k_lpc: frames per wave, 0 = by launch size (env NNN_LPC_FC; tests)
-    int lpc_wide = -1;              // k_lpc_wide (one lag per wave): -1 = for launches below 512 waves, 0 / 1 = never / always (env NNN_LPC_WIDE; tests)
     uint64_t id = 0, other_seen_us = 0;   // see g_call_mark
     bool beside_others = false;     // as of the current call
     bool host_call = false;         // inside a host-buffer entry point: the input is an upload enqueued by this library, final only in stream order
@@ -193,16 +255,7 @@ struct nnn_batch {
     hipStream_t last_stream = nullptr;
     bool have_last = false;
     uint64_t call_count = 0;
-    int sched = SCHED_LANES;        // how a multi-frame call spreads over streams (env NNN_SCHED: seq | lanes | stages)
-    bool sched_auto = true;         // nobody chose a schedule (NNN_SCHED / NNN_LANES / nnn_batch_set_schedule): lanes up to 16384 streams, one stream above
-    int n_lanes = 1;                // SCHED_LANES: lanes (the caller's stream + internal ones) besides the high-pass stream; env NNN_LANES, 1..4.
-                                    // One since the end of round 3: with the frames of a group side by side in every kernel a second group in flight
-                                    // only gets in the first one's way (4096 streams: 55.5 against 54.8 M frames/s, 16 384: 63.8 / 62.3; profiles AN)
-                                    // (measured at 4096 streams x 48 frames: 1: 28.5, 2: 37.1, 3: 32.9, 4: 32.2 M frames/s -- the default 4 hardware
-                                    // queues are shared with the host's own streams)
-    int pitch_chain = 1;            // k_pitch: one workgroup per (frame, quarter tile) instead of a frame loop: 1 = below 16384 streams, 0 = never, 2 = always (env NNN_PITCH_CHAIN)
     bool taps_alloc = false;        // the tap-only scratch arrays exist
-    bool use_pipeline = true;       // nnn_batch_set_pipeline
     bool profiling = false;
     std::vector<hipEvent_t> evp;    // pairs per launch while profiling
     std::vector<int> evp_kernel;
@@ -320,6 +373,7 @@ extern "C" void nnn_batch_destroy(nnn_batch *h)
     if (h->ss_idx_pin) hipHostFree(h->ss_idx_pin);
     if (h->ev_ss_idx) hipEventDestroy(h->ev_ss_idx);
     if (h->ss_stage) hipFree(h->ss_stage);
+    delete[] h->plan.rnn;
     for (int i = 0; i < NSTREAMS; i++)
         if (h->pool[i]) hipStreamDestroy(h->pool[i]);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -347,7 +401,7 @@ static size_t rnn_wf_lds_bytes(const WfPlan &w)
 // (measured at 1024 / 4096 / 16384 streams, profiles/r1_e_rnn_rows.txt)
 constexpr int RNN_SMALL_BATCH_BLOCKS = 128;
 
-static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *group_streams, int n_groups, int device, int gmax)
+static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *group_streams, int n_groups, int device, int gmax, const Paths &paths)
 {
     h->gmax = gmax < 1 ? 1 : (gmax > GROUP ? GROUP : gmax);
     int n_streams = 0;
@@ -373,33 +427,10 @@ static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *g
             for (int i = 0; i < EVR; i++) HIPCHK(hipEventCreateWithFlags(&h->ev[p][s][i], hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&h->ev_done[p], hipEventDisableTiming));
     }
-    if (const char *e = knob("NNN_HOST_CHUNK")) h->host_chunk = atoi(e);
-    if (const char *e = knob("NNN_RNN_WF_MIN_G")) h->wf_min_g = atoi(e);
-    if (const char *e = knob("NNN_HP_SPLIT")) h->hp_split = atoi(e);
-    if (const char *e = dev_knob("NNN_HP_TPB")) h->hp_tpb = atoi(e);
-    if (const char *e = knob("NNN_LPC_HEAD")) h->lpc_head = atoi(e);
-    if (const char *e = dev_knob("NNN_X_RIDES")) h->x_rides = atoi(e);
-    if (const char *e = knob("NNN_PITCH_CHAIN")) h->pitch_chain = atoi(e);
-    if (const char *e = dev_knob("NNN_LPC_WIDE")) h->lpc_wide = atoi(e);
-    if (const char *e = dev_knob("NNN_LPC_FC")) h->lpc_fc = atoi(e);
-    if (const char *e = knob("NNN_SCHED")) {
-        if (!strcmp(e, "seq")) h->sched = SCHED_SEQ;
-        else if (!strcmp(e, "lanes")) h->sched = SCHED_LANES;
-        else if (!strcmp(e, "stages")) h->sched = SCHED_STAGES;
-        h->sched_auto = false;
-    }
-    if (const char *e = knob("NNN_LANES")) {
-        const int v = atoi(e);
-        if (v >= 1 && v <= NSTREAMS - 1) h->n_lanes = v;
-        h->sched_auto = false;
-    }
-    if (const char *e = knob("NNN_RNN_ROWS")) {
-        const int v = atoi(e);
-        if (v == 16 || v == 32) h->rnn_rows = v;
-    }
+    h->paths = h->created = paths;
     // groups in flight behind the high-pass: what the schedule chosen at creation can use (a schedule set later works on what is there).
-    // Nobody choosing, batches above AUTO_BIG streams keep two groups in flight (round 6, see process_frames: their calls overlap kernels).
-    h->depth = (h->n_lanes >= 2 || h->sched == SCHED_STAGES || (h->sched_auto && (n_streams + TILE - 1) / TILE * TILE > AUTO_BIG)) ? DEPTH : 1;
+    // Nobody choosing, batches above AUTO_BIG streams keep two groups in flight (round 6, see plan_call: their calls overlap kernels).
+    h->depth = (paths.n_lanes >= 2 || paths.sched == SCHED_STAGES || (paths.sched_auto && (n_streams + TILE - 1) / TILE * TILE > AUTO_BIG)) ? DEPTH : 1;
     h->nset = h->depth * h->gmax;
     h->nslot = slots_for(h->gmax, h->depth);
     h->S = n_streams;
@@ -436,7 +467,7 @@ static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *g
             if (rnn_lds_bytes(G.plan, rows) <= kLdsMax) G.rows = rows;
         if (!G.rows) return fail("model too large for the RNN kernel's LDS operand matrices");
         while (G.rows > 16 && G.ntiles * (TILE / G.rows) < RNN_SMALL_BATCH_BLOCKS) G.rows /= 2;
-        if (h->rnn_rows && rnn_lds_bytes(G.plan, h->rnn_rows) <= kLdsMax) G.rows = h->rnn_rows;
+        if (paths.rnn_rows && rnn_lds_bytes(G.plan, paths.rnn_rows) <= kLdsMax) G.rows = paths.rnn_rows;
         G.rnn_lds = rnn_lds_bytes(G.plan, G.rows);
         // models of the built-in shape class run the layer-pipelined kernel (its fixed wave roles cover 2 / 2 / 3 / 6 neuron
         // blocks in the input dense / vad / noise / denoise layers)
@@ -452,7 +483,7 @@ static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *g
             G.rnn16_lds = shape_ok && rb <= kLdsMax ? rb : 0;
             G.acts = BkActs{G.plan.dense.act, G.plan.vad.act, G.plan.noise.act, G.plan.dn.act, G.plan.out.act, G.plan.act_vo};
         }
-        G.wf = !h->rnn_rows && G.plan.dense.nb <= 2 && G.plan.vad.nb <= 2 && G.plan.noise.nb <= 3 && G.plan.dn.nb <= 6 && G.plan.vad.rec.ksteps <= WF_KS_REC &&
+        G.wf = !paths.rnn_rows && G.plan.dense.nb <= 2 && G.plan.vad.nb <= 2 && G.plan.noise.nb <= 3 && G.plan.dn.nb <= 6 && G.plan.vad.rec.ksteps <= WF_KS_REC &&
                G.plan.noise.rec.ksteps <= WF_KS_REC && G.plan.dn.rec.ksteps <= WF_KS_REC && G.wf_lds <= kLdsMax;   // (k_rnn_wf's wave roles)
         tile0 += G.ntiles;
         h->md.nd = md.nd > h->md.nd ? md.nd : h->md.nd;
@@ -461,6 +492,7 @@ static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *g
         h->md.ndn = md.ndn > h->md.ndn ? md.ndn : h->md.ndn;
     }
     const ModelDims &md = h->md;
+    h->plan.rnn = new uint8_t[n_groups]();
 
     Buffers &b = h->b[0];
     memset(&b, 0, sizeof(b));
@@ -572,6 +604,19 @@ static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *g
     return 0;
 }
 
+static nnn_batch *create_batch(const RNNModel *const *models, const int *group_streams, int n_groups, int device, int gmax, const Paths &paths)
+{
+    NNN_RT_LOCK;
+    nnn_batch *h = new nnn_batch();
+    if (create_impl(h, models, group_streams, n_groups, device, gmax, paths) != 0) {
+        std::string keep = g_err;
+        nnn_batch_destroy(h);
+        g_err = keep;
+        return nullptr;
+    }
+    return h;
+}
+
 extern "C" nnn_batch *nnn_batch_create_opts(const RNNModel *const *models, const int *group_streams, int n_groups, int device,
                                              const nnn_batch_opts *opts)
 {
@@ -596,15 +641,7 @@ extern "C" nnn_batch *nnn_batch_create_opts(const RNNModel *const *models, const
         }
         if (opts->max_group_frames > 0) gmax = opts->max_group_frames;
     }
-    NNN_RT_LOCK;
-    nnn_batch *h = new nnn_batch();
-    if (create_impl(h, models, group_streams, n_groups, device, gmax) != 0) {
-        std::string keep = g_err;
-        nnn_batch_destroy(h);
-        g_err = keep;
-        return nullptr;
-    }
-    return h;
+    return create_batch(models, group_streams, n_groups, device, gmax, read_paths());
 }
 
 extern "C" nnn_batch *nnn_batch_create_grouped(const RNNModel *const *models, const int *group_streams, int n_groups, int device)
@@ -738,9 +775,8 @@ extern "C" nnn_batch *nnn_batch_clone(nnn_batch *h)
     if (quiesce(h)) return nullptr;
     std::vector<const RNNModel *> mp;
     for (const RNNModel &m : h->models) mp.push_back(&m);
-    nnn_batch_opts o = {};
-    o.max_group_frames = h->gmax;
-    nnn_batch *c = nnn_batch_create_opts(mp.data(), h->group_streams.data(), (int)h->group_streams.size(), h->device, &o);
+    // made as the source was made (not from the environment of now: its depth, ring and kernel forms must match), then set as it is
+    nnn_batch *c = create_batch(mp.data(), h->group_streams.data(), (int)h->group_streams.size(), h->device, h->gmax, h->created);
     if (!c) return nullptr;
     bool ok = c->state_bufs.size() == h->state_bufs.size();
     for (size_t i = 0; ok && i < h->state_bufs.size(); i++)
@@ -753,19 +789,7 @@ extern "C" nnn_batch *nnn_batch_clone(nnn_batch *h)
     }
     c->frame_count = h->frame_count;
     c->group_count = h->group_count;
-    c->sched = h->sched;
-    c->sched_auto = h->sched_auto;
-    c->n_lanes = h->n_lanes;
-    c->use_pipeline = h->use_pipeline;
-    c->pitch_chain = h->pitch_chain;
-    c->back_mode = h->back_mode;
-    c->hp_split = h->hp_split;
-    c->hp_tpb = h->hp_tpb;
-    c->lpc_head = h->lpc_head;
-    c->x_rides = h->x_rides;
-    c->lpc_wide = h->lpc_wide;
-    c->lpc_fc = h->lpc_fc;
-    c->inputs_ready = h->inputs_ready;
+    c->paths = h->paths;
     if (h->b[0].taps && nnn_batch_set_taps(c, h->b[0].taps) != 0) {
         nnn_batch_destroy(c);
         return nullptr;
@@ -1239,105 +1263,107 @@ struct Launcher {
 
 // Per-group DAG: hp -> pitch -> fft_xp -> rnn -> synth.  Four stages carry state from group to group -- the
 // biquad (hp), the last pitch (pitch), GRU / cepstral / last-gain state (rnn), the overlap memory (synth).
-// stage `s` of the group of `g` frames in scratch sets set0 .. set0 + g - 1, parameters at sp0[0..g), on stream `st`
-// which back end a group of g frames takes: 0 = k_fft_xp -> k_rnn / k_rnn_wf -> k_synth, 1 = the same with k_back<false> as the RNN, 2 = k_back<true>
-// (the fused back end).  One-frame groups by default: there the unfused chain's three launches and the round trip of the spectra through
-// HBM buy nothing -- the layer-pipelined RNN has no second frame to pipeline.
-static int back_choice(const nnn_batch *h, int g)
+
+// The LPC analysis of a group's frames as a launch of its own behind the high-pass (lane = stream, frames side by side): launches too
+// small to fill the GPU spread the five lags of a stream over five waves (k_lpc_wide); k_lpc takes as many frames per wave as still
+// leave two waves per SIMD (the frames per wave; 0 = k_lpc_wide).  The denoiser (plan_group) and the training rows launch it so.
+static int lpc_launch(const nnn_batch *h, int g)
 {
-    int m = h->back_mode;
-    if (m < 0) {
-        // Measured on one MI355X (scripts/back_ab.py, profiles/r4_back_ab.txt), one frame per call: fused 143 us against 162 (unfused) and
-        // 148 (RNN stretch alone) at 4096 streams, level with the RNN stretch alone at 8192, behind it from 16 384 streams up (a block of
-        // sixteen waves that holds a compute unit through three stretches fills the GPU worse than three launches of small blocks once
-        // there are several rounds of them); 24-frame groups: the layer-pipelined RNN between k_fft_xp and k_synth stays ahead of
-        // both (65.5 against 59.7 M frames/s at 65 536 streams).
-        if (g > 1) return 0;
-        m = (h->S_pad <= 8192 && !h->beside_others) ? 1 : 3;
-    }
-    if (m == 0) return 0;
+    const Paths &p = h->paths;
+    const unsigned NT = (unsigned)h->NT, ug = (unsigned)g;
+    if (p.lpc_wide >= 0 ? p.lpc_wide != 0 : NT * ug < 512u) return 0;
+    int fc = LPC_FC;
+    while (fc > 1 && NT * ((ug + fc - 1) / fc) < 2048u) fc /= 2;
+    if (p.lpc_fc > 0) fc = p.lpc_fc < LPC_FC ? p.lpc_fc : LPC_FC;
+    return fc;
+}
+// k_pitch's frames side by side, chained through flags, while one frame's workgroups cannot fill the GPU (below 16384 streams; measured
+// at 4096: 46.8 -> 32.8 us per frame; at 65536, where the frame loop's prefetch of the next window matters instead: 468 -> 515)
+static bool pitch_chained(const nnn_batch *h, int g)
+{
+    const int pc = h->paths.pitch_chain;
+    return pc > 0 && g > 1 && (pc > 1 || (unsigned)h->S_pad / PK_SPB < 1024u);
+}
+
+// Everything a group of g frames runs, into p.  Reads the batch only.
+static void plan_group(const nnn_batch *h, int g, GroupPlan &p)
+{
+    const Paths &k = h->paths;
+    p.g = g;
+    // The back end.  One-frame groups by default: there the unfused chain's three launches and the round trip of the spectra through
+    // HBM buy nothing -- the layer-pipelined RNN has no second frame to pipeline.  Measured on one MI355X
+    // (scripts/back_ab.py, profiles/r4_back_ab.txt), one frame per call: fused 143 us against 162 (unfused) and 148 (RNN stretch alone)
+    // at 4096 streams, level with the RNN stretch alone at 8192, behind it from 16 384 streams up (a block of sixteen waves that holds a
+    // compute unit through three stretches fills the GPU worse than three launches of small blocks once there are several rounds of
+    // them); 24-frame groups: the layer-pipelined RNN between k_fft_xp and k_synth stays ahead of both (65.5 against 59.7 M frames/s at
+    // 65 536 streams).
+    const int m = k.back_mode >= 0 ? k.back_mode : g > 1 ? 0 : ((h->S_pad <= 8192 && !h->beside_others) ? 1 : 3);
     const bool fused = m == 1 || m == 2, all_g = m == 2 || m == 4;
-    if (g > 1 && !all_g) return 0;
+    p.back = m == 0 || (g > 1 && !all_g) ? BACK_UNFUSED : (fused ? BACK_FUSED : BACK_RNN_ALONE);
     for (const nnn_batch::ModelGroup &G : h->groups)
-        if ((fused ? G.back_lds : G.rnn16_lds) == 0) return 0;
-    return fused ? 2 : 1;
+        if ((fused ? G.back_lds : G.rnn16_lds) == 0) p.back = BACK_UNFUSED;   // (a model outside the kernel's shape class)
+    // k_hp on two waves per tile (recurrence | everything else, k_hp2): for launches that leave SIMDs empty; groups: two tiles per block
+    const bool split = k.hp_split >= 0 ? k.hp_split != 0 : h->NT <= 256;
+    p.hp = !split ? 0 : ((k.hp_tpb ? k.hp_tpb == 2 : (g > 1 && h->NT >= 8)) ? 2 : 1);
+    // One-frame groups of batches whose pitch launch is a single round of workgroups (two 8-wave blocks per compute unit) run the LPC
+    // analysis inside k_pitch: one launch fewer on the critical path of a real-time tick (measured per one-frame call: -6 us at 4096
+    // streams, level at 8192, +9 us at 16 384).  With k_hp2, the part of its sums that needs none of the new frame rides in the
+    // high-pass launch (the head: another -5 us at 4096, -6 at 8192, still +10 at 16 384).
+    p.lpc_in_pitch = g == 1 && h->S_pad <= (split ? 8192 : 6144) && k.lpc_wide < 0 && k.lpc_fc == 0;
+    p.head = p.lpc_in_pitch && split && k.lpc_head != 0;
+    p.lpc_fc = p.lpc_in_pitch ? 0 : lpc_launch(h, g);
+    p.chain = pitch_chained(h, g);
+    // one-frame groups through the fused back end on small batches: its X transform rides in k_pitch's launch
+    p.riders = g == 1 && p.back == BACK_FUSED && (k.x_rides >= 0 ? k.x_rides != 0 : h->S_pad <= 8192);
+    // The RNN kernel of each resident model.  The layer-pipelined kernel spends g + 4 ticks on g frames: for a lone frame on a batch of
+    // many block rounds the plain kernel's eleven phases are shorter (one frame per call at 16 384 / 32 768 / 65 536 streams: +6 / +7 /
+    // +7 %; at 4096 streams, one round of blocks, the pipelined kernel stays 8 % ahead).  Same bits either way.
+    // ... and with other batches ticking beside this one (g_call_mark) the lone frame's kernel is chosen for their sake too (k_rnn_wf holds
+    // every compute unit for its five ticks: eight 4096-stream batches ticking side by side 40.2 -> 43.4 M frames/s with k_rnn, a lone batch -8 %)
+    for (size_t i = 0; i < h->groups.size(); i++) {
+        const nnn_batch::ModelGroup &G = h->groups[i];
+        const int min_g = k.wf_min_g > 0 ? k.wf_min_g : ((G.ntiles * (TILE / WF_ROWS) >= 1024 || h->beside_others) ? 2 : 1);
+        p.rnn[i] = p.back == BACK_RNN_ALONE ? RK_BACK : !(G.wf && g >= min_g) ? RK_PLAIN : G.shape_builtin ? RK_WF_BUILTIN : RK_WF_ANY;
+    }
 }
-// one-frame groups of batches whose pitch launch is a single round of workgroups (two 8-wave blocks per compute unit)
-// run the LPC analysis inside k_pitch: one launch fewer on the critical path of a real-time tick
-// k_hp on two waves per tile (recurrence | everything else): for launches that leave SIMDs empty
-static bool hp_split(const nnn_batch *h)
-{
-    if (h->hp_split >= 0) return h->hp_split != 0;
-    return h->NT <= 256;
-}
-static bool lpc_in_pitch(const nnn_batch *h, int g)
-{
-    // (measured per one-frame call: -6 us at 4096 streams, level at 8192, +9 us at 16 384; with the sums' head start in k_hp2's launch, see
-    // lpc_head: another -5 us at 4096, -6 at 8192, still +10 at 16 384)
-    return g == 1 && h->S_pad <= (hp_split(h) ? 8192 : 6144) && h->lpc_wide < 0 && h->lpc_fc == 0;
-}
-// one-frame calls through the fused back end on small batches: its X transform rides in k_pitch's launch (env NNN_X_RIDES=0|1, read at creation)
-static bool x_rides(const nnn_batch *h, int g, int back)
-{
-    if (g != 1 || back != 2) return false;
-    return h->x_rides >= 0 ? h->x_rides != 0 : h->S_pad <= 8192;
-}
-static bool lpc_head(const nnn_batch *h, int g)
-{
-    return lpc_in_pitch(h, g) && hp_split(h) && h->lpc_head != 0;
-}
+
+// stage `s` of the group planned in p, in scratch sets set0 .. set0 + p.g - 1, parameters at sp0[0..g), on stream `st`.
 // plain_out: the parameter table sp0 points into was filled for f32 mono audio (k_synth's plain-format instantiation ignores the table's
 // fmt / channels, so the caller states the format of the very call that fills the table, not a field of the batch)
-static void launch_stage(nnn_batch *h, int s, int set0, int g, const StepParams *sp0, hipStream_t st, bool prof, bool plain_out, const StepParams *call = nullptr, int fill = 0)
+static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, const StepParams *sp0, hipStream_t st, bool prof, bool plain_out, const StepParams *call = nullptr, int fill = 0)
 {
+    const int g = p.g;
     if (g <= 0) return;   // (never a launch with an empty grid)
     const unsigned NT = (unsigned)h->NT, Sp = (unsigned)h->S_pad, ug = (unsigned)g;
     const Buffers &b = h->b[set0];
     Launcher L{h, st, prof};
-    const int back = back_choice(h, g);
     switch (s) {
     case ST_HP:
         // (`fill`: this is the first launch of a call whose parameter table is k_hp's to fill, see k_hp)
-        if (hp_split(h)) {
-            // (a lone frame whose LPC analysis runs inside k_pitch: the part of its sums that needs none of the new frame rides along here)
-            const bool head = lpc_head(h, g);
-            // groups: two tiles per block (see k_hp2)
-            if (h->hp_tpb ? h->hp_tpb == 2 : (g > 1 && NT >= 8))
-                L.go(K_HP, k_hp2<2>, dim3((NT + 1) / 2 + (head ? (5 * NT + 3) / 4 : 0)), dim3(256), 0, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0, head ? 1 : 0);
-            else
-                L.go(K_HP, k_hp2<1>, dim3(NT + (head ? (5 * NT + 1) / 2 : 0)), dim3(128), 0, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0, head ? 1 : 0);
-        }
+        if (p.hp == 2)
+            L.go(K_HP, k_hp2<2>, dim3((NT + 1) / 2 + (p.head ? (5 * NT + 3) / 4 : 0)), dim3(256), 0, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0, p.head ? 1 : 0);
+        else if (p.hp == 1)
+            L.go(K_HP, k_hp2<1>, dim3(NT + (p.head ? (5 * NT + 1) / 2 : 0)), dim3(128), 0, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0, p.head ? 1 : 0);
         else L.go(K_HP, k_hp, dim3(NT), dim3(64), 0, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0);
-        // the LPC analysis of the group's frames (lane = stream, frames side by side) rides on the same stream, ahead of the pitch stage
-        // (launches too small to fill the GPU spread the five lags of a stream over five waves)
-        if (lpc_in_pitch(h, g)) break;   // (a lone frame of a small batch: k_pitch does it on its way, see there)
-        if (h->lpc_wide >= 0 ? h->lpc_wide != 0 : NT * ug < 512u) L.go(K_LPC, k_lpc_wide, dim3(NT * ug), dim3(320), 0, b, sp0, g);
-        else {
-            // frames per wave (k_lpc): as many as still leave two waves per SIMD
-            int fc = LPC_FC;
-            while (fc > 1 && NT * ((ug + fc - 1) / fc) < 2048u) fc /= 2;
-            if (h->lpc_fc > 0) fc = h->lpc_fc < LPC_FC ? h->lpc_fc : LPC_FC;
-            L.go(K_LPC, k_lpc, dim3(NT * ((ug + fc - 1) / fc)), dim3(64), 0, b, sp0, g, fc);
-        }
+        if (p.lpc_in_pitch) break;   // (k_pitch does it on its way, see there)
+        if (!p.lpc_fc) L.go(K_LPC, k_lpc_wide, dim3(NT * ug), dim3(320), 0, b, sp0, g);
+        else L.go(K_LPC, k_lpc, dim3(NT * ((ug + p.lpc_fc - 1) / p.lpc_fc)), dim3(64), 0, b, sp0, g, p.lpc_fc);
         break;
     case ST_PITCH: {
-        // frames side by side, chained through flags (k_pitch), while one frame's workgroups cannot fill the GPU (below 16384
-        // streams; measured at 4096: 46.8 -> 32.8 us per frame; at 65536, where the frame loop's prefetch of the next window
-        // matters instead: 468 -> 515); flag values are frame numbers (> 0)
-        const int chain = h->pitch_chain > 0 && g > 1 && (h->pitch_chain > 1 || Sp / PK_SPB < 1024u), seq0 = (int)(h->frame_count & 0x3fffffffu) + 1;
+        // (flag values are frame numbers (> 0))
+        const int chain = p.chain ? 1 : 0, seq0 = (int)(h->frame_count & 0x3fffffffu) + 1;
         const unsigned grid = Sp / PK_SPB * (chain ? ug : 1u);
-        const bool riders = x_rides(h, g, back);   // (the fused back end's X transform in rider blocks of this launch, see xt_rider)
-        if (lpc_in_pitch(h, g))
-            L.go(K_PITCH, k_pitch<true>, dim3(grid + (riders ? Sp / 8 : 0u)), dim3(PK_T), 0, b, sp0, g, chain, seq0, h->tickets, lpc_head(h, g) ? 2 : 1, riders ? (int)grid : 0);
+        if (p.lpc_in_pitch)
+            L.go(K_PITCH, k_pitch<true>, dim3(grid + (p.riders ? Sp / 8 : 0u)), dim3(PK_T), 0, b, sp0, g, chain, seq0, h->tickets, p.head ? 2 : 1, p.riders ? (int)grid : 0);
         else
-            L.go(K_PITCH, k_pitch<false>, dim3(grid + (riders ? Sp / 8 : 0u)), dim3(PK_T), 0, b, sp0, g, chain, seq0, h->tickets, 0, riders ? (int)grid : 0);
+            L.go(K_PITCH, k_pitch<false>, dim3(grid + (p.riders ? Sp / 8 : 0u)), dim3(PK_T), 0, b, sp0, g, chain, seq0, h->tickets, 0, p.riders ? (int)grid : 0);
         if (chain) h->tickets += grid;   // (launches of one batch's pitch stage are ordered among themselves: a stateful stage)
         break;
     }
     case ST_FFT:
-        if (back == 2) {   // the fused back end takes the place of this stage and the two behind it: one launch per resident model
+        if (p.back == BACK_FUSED) {   // the fused back end takes the place of this stage and the two behind it: one launch per resident model
             for (const nnn_batch::ModelGroup &G : h->groups) {
-                if (x_rides(h, g, back))
+                if (p.riders)   // (its X transform done by k_pitch's rider blocks, see xt_rider)
                     L.go(K_BACK, k_back<true, BkShapeBuiltin, true>, dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.back_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
                 else
                     L.go(K_BACK, k_back<true, BkShapeBuiltin>, dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.back_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
@@ -1347,32 +1373,24 @@ static void launch_stage(nnn_batch *h, int s, int set0, int g, const StepParams 
         L.go(K_FFT_XP, k_fft_xp, dim3(Sp * ug / FFT_SPB), dim3(64 * FFT_SPB), 0, b, sp0, g);
         break;
     case ST_RNN:
-        if (back == 2) break;
-        for (const nnn_batch::ModelGroup &G : h->groups) {   // one launch per resident model (a run of whole tiles)
-            if (back == 1) {
+        if (p.back == BACK_FUSED) break;
+        for (size_t i = 0; i < h->groups.size(); i++) {   // one launch per resident model (a run of whole tiles)
+            const nnn_batch::ModelGroup &G = h->groups[i];
+            if (p.rnn[i] == RK_BACK)
                 L.go(K_RNN, k_back<false, BkShapeBuiltin>, dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.rnn16_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
-                continue;
-            }
-            // the layer-pipelined kernel spends g + 4 ticks on g frames: for a lone frame on a batch of many block rounds the
-            // plain kernel's eleven phases are shorter (one frame per call at 16 384 / 32 768 / 65 536 streams: +6 / +7 / +7 %;
-            // at 4096 streams, one round of blocks, the pipelined kernel stays 8 % ahead).  Same bits either way.
-            // ... and with other batches ticking beside this one (g_call_mark) the lone frame's kernel is chosen for their sake too (k_rnn_wf holds every compute unit
-            // for its five ticks: eight 4096-stream batches ticking side by side 40.2 -> 43.4 M frames/s with k_rnn, a lone batch -8 %)
-            const int min_g = h->wf_min_g > 0 ? h->wf_min_g : ((G.ntiles * (TILE / WF_ROWS) >= 1024 || h->beside_others) ? 2 : 1);
-            if (G.wf && g >= min_g) {
-                if (G.shape_builtin)
-                    L.go(K_RNN, k_rnn_wf<BkShapeBuiltin>, dim3((unsigned)(G.ntiles * (TILE / WF_ROWS))), dim3(64 * WF_WAVES), G.wf_lds, b, G.plan, G.wp,
-                         G.wq, G.fpar, G.tile0, g);
-                else
-                    L.go(K_RNN, k_rnn_wf<WfShapeAny>, dim3((unsigned)(G.ntiles * (TILE / WF_ROWS))), dim3(64 * WF_WAVES), G.wf_lds, b, G.plan, G.wp,
-                         G.wq, G.fpar, G.tile0, g);
-            } else
+            else if (p.rnn[i] == RK_WF_BUILTIN)
+                L.go(K_RNN, k_rnn_wf<BkShapeBuiltin>, dim3((unsigned)(G.ntiles * (TILE / WF_ROWS))), dim3(64 * WF_WAVES), G.wf_lds, b, G.plan, G.wp,
+                     G.wq, G.fpar, G.tile0, g);
+            else if (p.rnn[i] == RK_WF_ANY)
+                L.go(K_RNN, k_rnn_wf<WfShapeAny>, dim3((unsigned)(G.ntiles * (TILE / WF_ROWS))), dim3(64 * WF_WAVES), G.wf_lds, b, G.plan, G.wp,
+                     G.wq, G.fpar, G.tile0, g);
+            else
                 L.go(K_RNN, k_rnn, dim3((unsigned)(G.ntiles * (TILE / G.rows))), dim3(64 * RNN_WAVES), G.rnn_lds, b, G.plan, G.wq, G.fpar,
                      G.tile0, G.rows, g);
         }
         break;
     case ST_SYN:
-        if (back == 2) break;
+        if (p.back == BACK_FUSED) break;
         if (plain_out) L.go(K_SYNTH, k_synth<true>, dim3(Sp / FFT_SPB), dim3(64 * FFT_SPB), 0, b, sp0, g);
         else L.go(K_SYNTH, k_synth<false>, dim3(Sp / FFT_SPB), dim3(64 * FFT_SPB), 0, b, sp0, g);
         break;
@@ -1393,6 +1411,61 @@ static int drain_profile(nnn_batch *h)
     h->evp.clear();
     h->evp_kernel.clear();
     return 0;
+}
+
+struct CallPlan {             // what a call decides before it launches anything (plan_call, which reads the batch only)
+    std::vector<int> sizes;   // frames of each group
+    bool pipe;                // spread over the internal streams (otherwise the groups' stages back to back on the caller's stream)
+    int sched, lanes;         // the schedule of a pipelined call
+    bool fold_fill, early_hp, hp_after;   // see plan_call
+};
+static CallPlan plan_call(const nnn_batch *h, int n_frames, hipStream_t st)
+{
+    const Paths &k = h->paths;
+    CallPlan c;
+    // group sizes.  A pipelined call (32 frames or more) is cut into an even number of near-equal groups of at most GROUP frames --
+    // its groups alternate between two lanes, so an odd count leaves one lane a group short (three groups of 16 for the bench's
+    // 48-frame call: 55.5 M frames/s at 4096 streams; two of 24: 57.2 M) -- everything else into full groups of GROUP frames, the
+    // remainder last (round 2a's smaller groups at the ends of a pipelined call measured 6 % slower).
+    constexpr int PIPE_MIN = 32;
+    // (from 16 384 streams up every kernel fills the GPU on its own and a launch beside it only costs it cache: one stream, in order,
+    // unless a schedule was asked for -- 32 768 streams: 65.9 M frames/s against 64.8 with the high-pass on a stream of its own)
+    // (the automatic schedule pipelines up to 16 384 streams: measured in round 4 with the high-pass held back behind the previous group's
+    // pitch kernel, see hp_after -- 16 384: 64.2-65.5 -> 66.4-66.9 M frames/s; 32 768 and 65 536 lose 1-2 % pipelined)
+    // Round 6: above 16 384 streams the automatic schedule overlaps kernels again.  k_pitch issues a fifth fewer instructions than in round 5 and
+    // waits more (certified search), and every kernel of a big batch ends in a tail of half-empty compute units -- twelve tails per 48-frame
+    // call; with two groups in flight another stage's blocks fill them.  Measured on one box, interleaved (scripts/gpu_sched_r6.sh,
+    // profiles/r6_sched_sweep.txt), against one stream in order: 65 536 x 48 stages +2.6 % (lanes 2: +1.0), 65 536 x 96 lanes 2 +2.3 % (stages
+    // -0.3), 32 768 x 96 lanes 2 +1.9 % (stages +0.4), 32 768 x 48 stages +1.0 % (lanes 2: -0.4): one stream per stage for calls of two
+    // groups, two lanes for longer ones.  Costs the second block of scratch sets and the longer ring (650 against 360 KB per stream).
+    const bool auto_big = k.sched_auto && h->S_pad > AUTO_BIG;
+    c.pipe = k.use_pipeline && k.sched != SCHED_SEQ && !h->profiling && n_frames >= PIPE_MIN && !(auto_big && h->depth < 2);
+    if (c.pipe) {
+        int n = 2;
+        while ((n_frames + n - 1) / n > h->gmax) n += 2;
+        // (a batch sized for one-frame groups and an odd frame count: the even count overshoots the frames -- never an empty group)
+        if (n > n_frames) n = n_frames;
+        for (int i = 0; i < n; i++) c.sizes.push_back(n_frames / n + (i < n_frames % n ? 1 : 0));
+    } else {
+        for (int rem = n_frames; rem > 0; rem -= c.sizes.back()) c.sizes.push_back(rem < h->gmax ? rem : h->gmax);
+    }
+    c.sched = auto_big ? (c.sizes.size() <= 2 ? SCHED_STAGES : SCHED_LANES) : k.sched;
+    c.lanes = auto_big ? 2 : k.n_lanes;
+    // the per-frame parameter table: a launch of its own ahead of a pipelined call's streams; otherwise the call's first kernel (k_hp of
+    // the first group) fills it on its way (a one-frame call is a handful of launches of 15-35 us: one fewer is 4 % of it)
+    c.fold_fill = !c.pipe && !h->profiling;
+    // The next call's high-pass chain may start before this stream has seen the previous call drain, when the caller has
+    // promised that inputs are final at call time (nnn_batch_set_inputs_ready): it depends on the previous call only through
+    // its own stream (biquad state) and the history-ring slots it overwrites (synthesis events of the groups that read them).
+    // (never for the library's own host-buffer calls: their input is an upload enqueued just before on the caller's stream or on
+    // a copy stream, final only in that stream's order -- the promise is about buffers the CALLER filled)
+    c.early_hp = c.pipe && k.inputs_ready && !h->host_call && h->prev_pipe && h->prev_st == st && c.sched == SCHED_LANES && h->pool[0];
+    // The high-pass of group k may start as soon as the ring slots it overwrites are free -- with the pitch kernel of group k - 1, and the
+    // two slow each other (10.8 in HISTORY.md).  From 8192 streams up a group is long enough for the chain to wait until that pitch
+    // kernel is done and still finish before group k needs it: 8192 x 48: 61.3 -> 63.9 M frames/s, 16 384: +2-3 %; at 4096 streams the
+    // window is too short (57.5 -> 56.3).
+    c.hp_after = c.sched == SCHED_LANES && c.lanes == 1 && h->S_pad >= 8192;
+    return c;
 }
 
 // Common body of the process entry points: strides in BYTES, `drop` leading frames of the call produce no audio.
@@ -1459,61 +1532,26 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
         h->sp_tab_cap = cap;
         h->prev_pipe = false;
     }
-    // group sizes.  A pipelined call (32 frames or more) is cut into an even number of near-equal groups of at most GROUP frames --
-    // its groups alternate between two lanes, so an odd count leaves one lane a group short (three groups of 16 for the bench's
-    // 48-frame call: 55.5 M frames/s at 4096 streams; two of 24: 57.2 M) -- everything else into full groups of GROUP frames, the
-    // remainder last (round 2a's smaller groups at the ends of a pipelined call measured 6 % slower).
-    constexpr int PIPE_MIN = 32;
-    // (from 16 384 streams up every kernel fills the GPU on its own and a launch beside it only costs it cache: one stream, in order,
-    // unless a schedule was asked for -- 32 768 streams: 65.9 M frames/s against 64.8 with the high-pass on a stream of its own)
-    // (the automatic schedule pipelines up to 16 384 streams: measured in round 4 with the high-pass held back behind the previous group's
-    // pitch kernel, see hp_after -- 16 384: 64.2-65.5 -> 66.4-66.9 M frames/s; 32 768 and 65 536 lose 1-2 % pipelined)
-    // Round 6: above 16 384 streams the automatic schedule overlaps kernels again.  k_pitch issues a fifth fewer instructions than in round 5 and
-    // waits more (certified search), and every kernel of a big batch ends in a tail of half-empty compute units -- twelve tails per 48-frame
-    // call; with two groups in flight another stage's blocks fill them.  Measured on one box, interleaved (scripts/gpu_sched_r6.sh,
-    // profiles/r6_sched_sweep.txt), against one stream in order: 65 536 x 48 stages +2.6 % (lanes 2: +1.0), 65 536 x 96 lanes 2 +2.3 % (stages
-    // -0.3), 32 768 x 96 lanes 2 +1.9 % (stages +0.4), 32 768 x 48 stages +1.0 % (lanes 2: -0.4): one stream per stage for calls of two
-    // groups, two lanes for longer ones.  Costs the second block of scratch sets and the longer ring (650 against 360 KB per stream).
-    const bool auto_big = h->sched_auto && h->S_pad > AUTO_BIG;
-    const bool pipe = h->use_pipeline && h->sched != SCHED_SEQ && !h->profiling && n_frames >= PIPE_MIN && !(auto_big && h->depth < 2);
-    std::vector<int> sizes;
-    if (pipe) {
-        int k = 2;
-        while ((n_frames + k - 1) / k > h->gmax) k += 2;
-        // (a batch sized for one-frame groups and an odd frame count: the even count overshoots the frames -- never an empty group)
-        if (k > n_frames) k = n_frames;
-        for (int i = 0; i < k; i++) sizes.push_back(n_frames / k + (i < n_frames % k ? 1 : 0));
-    } else {
-        for (int rem = n_frames; rem > 0; rem -= sizes.back()) sizes.push_back(rem < h->gmax ? rem : h->gmax);
-    }
-    const int n_groups = (int)sizes.size();
-    const int call_sched = auto_big ? (n_groups <= 2 ? SCHED_STAGES : SCHED_LANES) : h->sched, call_lanes = auto_big ? 2 : h->n_lanes;
+    const CallPlan cp = plan_call(h, n_frames, st);
+    const int n_groups = (int)cp.sizes.size();
     h->call_count += 1;
     const int par = (int)(h->call_count & 1);
     StepParams *const tab = h->sp_tab + (size_t)par * h->sp_tab_cap;   // this call's parameter table
     const uint64_t frame0 = h->frame_count;
     bool ok = true;
     auto chk = [&](hipError_t e) { ok = ok && e == hipSuccess; };
-    // The next call's high-pass chain may start before this stream has seen the previous call drain, when the caller has
-    // promised that inputs are final at call time (nnn_batch_set_inputs_ready): it depends on the previous call only through
-    // its own stream (biquad state) and the history-ring slots it overwrites (synthesis events of the groups that read them).
-    // (never for the library's own host-buffer calls: their input is an upload enqueued just before on the caller's stream or on
-    // a copy stream, final only in that stream's order -- the promise is about buffers the CALLER filled)
-    const bool early_hp = pipe && h->inputs_ready && !h->host_call && h->prev_pipe && h->prev_st == st && call_sched == SCHED_LANES && h->pool[0];
-    // the per-frame parameter table: a launch of its own ahead of a pipelined call's streams; otherwise the call's first kernel (k_hp of
-    // the first group) fills it on its way (a one-frame call is a handful of launches of 15-35 us: one fewer is 4 % of it)
-    const bool fold_fill = !pipe && !h->profiling;
-    if (early_hp) {
+    if (cp.early_hp) {
         if (h->have_done[par]) chk(hipStreamWaitEvent(h->pool[0], h->ev_done[par], 0));   // the table's previous user (two calls back)
         hipLaunchKernelGGL(k_fill_params, dim3((n_frames + 63) / 64), dim3(64), 0, h->pool[0], tab, v0, n_frames, h->nslot);
         h->pool_call[0] = h->call_count;   // (no wait for the caller's stream on this one)
-    } else if (!fold_fill) {
+    } else if (!cp.fold_fill) {
         hipLaunchKernelGGL(k_fill_params, dim3((n_frames + 63) / 64), dim3(64), 0, st, tab, v0, n_frames, h->nslot);
     }
-    if (!pipe) {
+    if (!cp.pipe) {
         for (int k = 0, t = 0; k < n_groups; k++) {
-            const int g = sizes[k], set0 = (int)(h->group_count % h->depth) * h->gmax;
-            for (int s = 0; s < ST_COUNT; s++) launch_stage(h, s, set0, g, tab + t, st, h->profiling, plain_out, (fold_fill && k == 0) ? &v0 : nullptr, n_frames);
+            const int g = cp.sizes[k], set0 = (int)(h->group_count % h->depth) * h->gmax;
+            plan_group(h, g, h->plan);
+            for (int s = 0; s < ST_COUNT; s++) launch_stage(h, s, set0, h->plan, tab + t, st, h->profiling, plain_out, (cp.fold_fill && k == 0) ? &v0 : nullptr, n_frames);
             h->group_count += 1;
             h->frame_count += g;
             h->last_set = set0 + g - 1;
@@ -1524,27 +1562,23 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
         chk(hipEventRecord(h->ev_in, st));
         // index into h->pool; -1 = the caller's stream (lane 0 of the lanes schedule, the synthesis chain of the stages one)
         auto stream_of = [&](int s, int k) -> int {
-            if (call_sched == SCHED_STAGES) return s == ST_HP ? 0 : (s == ST_PITCH ? 1 : (s == ST_FFT ? 2 : (s == ST_RNN ? 3 : -1)));
-            return s == ST_HP ? 0 : (k % call_lanes) - (k % call_lanes == 0 ? 1 : 0);
+            if (cp.sched == SCHED_STAGES) return s == ST_HP ? 0 : (s == ST_PITCH ? 1 : (s == ST_FFT ? 2 : (s == ST_RNN ? 3 : -1)));
+            return s == ST_HP ? 0 : (k % cp.lanes) - (k % cp.lanes == 0 ? 1 : 0);
         };
         std::vector<int> first(n_groups);   // first frame (within the call) of every group
-        for (int k = 0, t = 0; k < n_groups; k++) { first[k] = t; t += sizes[k]; }
+        for (int k = 0, t = 0; k < n_groups; k++) { first[k] = t; t += cp.sizes[k]; }
         // which (stage, group) nodes have a consumer on another stream: only those record an event
-        // The high-pass of group k may start as soon as the ring slots it overwrites are free -- with the pitch kernel of group k - 1, and the
-        // two slow each other (10.8 in HISTORY.md).  From 8192 streams up a group is long enough for the chain to wait until that pitch
-        // kernel is done and still finish before group k needs it: 8192 x 48: 61.3 -> 63.9 M frames/s, 16 384: +2-3 %; at 4096 streams the
-        // window is too short (57.5 -> 56.3).
-        const bool hp_after = call_sched == SCHED_LANES && call_lanes == 1 && h->S_pad >= 8192;
         auto consumers_elsewhere = [&](int s, int k) {
             const int me = stream_of(s, k);
             if (s + 1 < ST_COUNT && stream_of(s + 1, k) != me) return true;
             if ((s == ST_HP || s == ST_PITCH || s == ST_RNN || s == ST_SYN) && k + 1 < n_groups && stream_of(s, k + 1) != me) return true;
             if (s == ST_SYN) return true;   // scratch-set / ring edges and the end of the call
-            if (hp_after && s == ST_PITCH) return true;
+            if (cp.hp_after && s == ST_PITCH) return true;
             return false;
         };
         for (int k = 0; k < n_groups; k++) {
-            const int g = sizes[k], set0 = (int)(h->group_count % h->depth) * h->gmax;
+            const int g = cp.sizes[k], set0 = (int)(h->group_count % h->depth) * h->gmax;
+            plan_group(h, g, h->plan);
             for (int s = 0; s < ST_COUNT; s++) {
                 const int si = stream_of(s, k);
                 if (si >= 0 && !h->pool[si]) chk(hipStreamCreateWithFlags(&h->pool[si], hipStreamNonBlocking));
@@ -1560,10 +1594,10 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
                 if (s > 0) wait_for(s - 1, k);
                 if (s == ST_HP || s == ST_PITCH || s == ST_RNN || s == ST_SYN) wait_for(s, k - 1);
                 if (s == ST_PITCH) wait_for(ST_SYN, k - h->depth);
-                if (s == ST_HP && hp_after) {   // behind the previous group's pitch kernel (the previous call's last one for the first group)
+                if (s == ST_HP && cp.hp_after) {   // behind the previous group's pitch kernel (the previous call's last one for the first group)
                     const int pn = (int)h->prev_first.size();
                     if (k > 0) wait_for(ST_PITCH, k - 1);
-                    else if (early_hp && pn > 0) chk(hipStreamWaitEvent(ss, h->ev[h->prev_par][ST_PITCH][(pn - 1) % EVR], 0));
+                    else if (cp.early_hp && pn > 0) chk(hipStreamWaitEvent(ss, h->ev[h->prev_par][ST_PITCH][(pn - 1) % EVR], 0));
                 }
                 if (s == ST_HP) {
                     // slots written now held frames (newest of this group) - nslot and older; their last readers are the
@@ -1573,7 +1607,7 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
                     for (int j = 0; j < k; j++)
                         if (first[j] <= need) dk = j;
                     wait_for(ST_SYN, dk);
-                    if (early_hp && need < 0) {
+                    if (cp.early_hp && need < 0) {
                         // the frame lies in the previous call: the synthesis of its group there; older still: the call before that
                         const long long pn = (long long)frame0 + need - (long long)h->prev_frame0;
                         int pj = -1;
@@ -1583,7 +1617,7 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
                         else if (h->have_done[par]) chk(hipStreamWaitEvent(ss, h->ev_done[par], 0));   // (par = the call before the previous one)
                     }
                 }
-                launch_stage(h, s, set0, g, tab + first[k], ss, false, plain_out);
+                launch_stage(h, s, set0, h->plan, tab + first[k], ss, false, plain_out);
                 if (consumers_elsewhere(s, k)) chk(hipEventRecord(h->ev[par][s][k % EVR], ss));
             }
             h->group_count += 1;
@@ -1727,7 +1761,7 @@ static int process_host_span_impl(nnn_batch *h, const void *in, void *out, float
     // page-locked host memory directly (the input read over the link by the first kernel, audio and VAD written over it by the last): one
     // memcpy in, one wait, one memcpy out.  Same kernels, same bits.  An explicit NNN_HOST_CHUNK always takes the staged path below.
     constexpr size_t ZC_MAX = (size_t)1 << 20;
-    if (h->host_chunk < 0 && span + vbytes + 16 <= ZC_MAX) {
+    if (h->paths.host_chunk < 0 && span + vbytes + 16 <= ZC_MAX) {
         const size_t vofs = (span + 15) / 16 * 16;
         if (!h->zc_host) {
             NNN_RT_LOCK;
@@ -1781,7 +1815,7 @@ static int process_host_span_impl(nnn_batch *h, const void *in, void *out, float
     // against the link's own both-ways peak of 97 GB/s (profiles/r5_host_boundary.txt): 4096 streams x 48 frames f32 at 4 / 8 / 16-frame
     // chunks 84 / 79 / 69 GB/s both ways (round 4 used 8), 65 536 x 24 at 1 / 2 / 4 / 8: 90 / 87 / 81 / 71 (int16: 81 / 84 / 77 / 66).
     // Chunks under a megabyte are not worth their launches.
-    int chunk = h->host_chunk;
+    int chunk = h->paths.host_chunk;
     if (chunk < 0) {
         constexpr int HC = 16;   // longest chunk
         chunk = n_frames / 16;
@@ -2011,7 +2045,7 @@ extern "C" int nnn_batch_set_graph(nnn_batch *h, int on)
 extern "C" int nnn_batch_set_inputs_ready(nnn_batch *h, int on)
 {
     if (!h) return fail("null batch");
-    h->inputs_ready = on != 0;
+    h->paths.inputs_ready = on != 0;
     return 0;
 }
 // Parity-test record of every frame processed from now on (include/nnn_batch.h): device memory for `frames` frames.
@@ -2038,22 +2072,22 @@ extern "C" int nnn_batch_set_back_end(nnn_batch *h, int mode)
 {
     if (!h) return fail("null batch");
     if (mode < -1 || mode > 4) return fail("unknown back-end mode %d", mode);
-    h->back_mode = mode;
+    h->paths.back_mode = mode;
     return 0;
 }
 extern "C" int nnn_batch_set_pipeline(nnn_batch *h, int on)
 {
     if (!h) return fail("null batch");
-    h->use_pipeline = on != 0;
+    h->paths.use_pipeline = on != 0;
     return 0;
 }
 extern "C" int nnn_batch_set_schedule(nnn_batch *h, int mode, int lanes)
 {
     if (!h) return fail("null batch");
     if (mode < SCHED_SEQ || mode > SCHED_STAGES) return fail("unknown schedule %d", mode);
-    h->sched = mode;
-    if (lanes >= 1 && lanes <= NSTREAMS - 1) h->n_lanes = lanes;
-    h->sched_auto = false;
+    h->paths.sched = mode;
+    if (lanes >= 1 && lanes <= NSTREAMS - 1) h->paths.n_lanes = lanes;
+    h->paths.sched_auto = false;
     return 0;
 }
 
@@ -2125,14 +2159,10 @@ static void enqueue_feature_group(nnn_batch *h, hipStream_t st, const float *in,
     hipLaunchKernelGGL(k_fill_params, dim3(1), dim3(64), 0, st, sp, v, g, h->nslot);
     hipLaunchKernelGGL(k_hp, dim3(NT), dim3(64), 0, st, b, (const StepParams *)sp, g, StepParams{}, 0);
     if (full) {
-        if (h->lpc_wide >= 0 ? h->lpc_wide != 0 : NT * ug < 512u) hipLaunchKernelGGL(k_lpc_wide, dim3(NT * ug), dim3(320), 0, st, b, (const StepParams *)sp, g);
-        else {
-            int fc = LPC_FC;
-            while (fc > 1 && NT * ((ug + fc - 1) / fc) < 2048u) fc /= 2;
-            if (h->lpc_fc > 0) fc = h->lpc_fc < LPC_FC ? h->lpc_fc : LPC_FC;
-            hipLaunchKernelGGL(k_lpc, dim3(NT * ((ug + fc - 1) / fc)), dim3(64), 0, st, b, (const StepParams *)sp, g, fc);
-        }
-        const int chain = h->pitch_chain > 0 && g > 1 && (h->pitch_chain > 1 || Sp / PK_SPB < 1024u), seq0 = (int)(h->frame_count & 0x3fffffffu) + 1;
+        const int fc = lpc_launch(h, g);
+        if (!fc) hipLaunchKernelGGL(k_lpc_wide, dim3(NT * ug), dim3(320), 0, st, b, (const StepParams *)sp, g);
+        else hipLaunchKernelGGL(k_lpc, dim3(NT * ((ug + fc - 1) / fc)), dim3(64), 0, st, b, (const StepParams *)sp, g, fc);
+        const int chain = pitch_chained(h, g) ? 1 : 0, seq0 = (int)(h->frame_count & 0x3fffffffu) + 1;
         const unsigned grid = Sp / PK_SPB * (chain ? ug : 1u);
         hipLaunchKernelGGL(k_pitch<false>, dim3(grid), dim3(PK_T), 0, st, b, (const StepParams *)sp, g, chain, seq0, h->tickets, 0, 0);
         if (chain) h->tickets += grid;
@@ -2197,7 +2227,7 @@ extern "C" int nnn_train_process_host(nnn_train *t, const float *signal, const f
     // frame-major (a chunk: one run each).
     constexpr int HC = 16;   // frames per chunk (tuned on the bus, not tied to the kernels' group length)
     int C = n_frames > 2 * HC && S * HC * FRAME * 4 >= ((size_t)1 << 20) ? HC : n_frames;
-    if (h->host_chunk >= 0) C = h->host_chunk > 0 && h->host_chunk < n_frames ? h->host_chunk : n_frames;   // NNN_HOST_CHUNK (tests)
+    if (h->paths.host_chunk >= 0) C = h->paths.host_chunk > 0 && h->paths.host_chunk < n_frames ? h->paths.host_chunk : n_frames;   // NNN_HOST_CHUNK (tests)
     const int nch = (n_frames + C - 1) / C;
     if (int rc = host_copy_streams(h, nch)) return rc;
     const size_t pitch = (size_t)n_frames * FRAME * 4;

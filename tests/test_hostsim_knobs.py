@@ -37,3 +37,25 @@ def test_developer_knobs_are_not_in_the_product_build():
         blob = open(LIB_PATH, "rb").read()
         for name in re.findall(r'dev_knob\("(NNN_[A-Z_0-9]+)"\)', src):
             assert name.encode() + b"\0" not in blob, name
+
+
+@pytest.mark.parametrize("at_create,at_clone", [({"NNN_LANES": "2"}, {}), ({"NNN_SCHED": "stages"}, {}), ({}, {"NNN_SCHED": "stages"})])
+def test_clone_ignores_the_environment_of_the_moment(hostsim_lib, monkeypatch, at_create, at_clone):
+    """clone() is DenoiseState's Clone: the copy is made with the source's settings, whatever the environment says when it is made."""
+    import nnnoiseless_amd as nn
+    from nnnoiseless_amd.synthetic import make_streams
+    S = 3
+    x = make_streams(11, S, 37)
+    for k, v in at_create.items():
+        monkeypatch.setenv(k, v)
+    a = nn.BatchDenoiser(S, lib=hostsim_lib)
+    a.process(x[:, :3])
+    for k in ("NNN_SCHED", "NNN_LANES"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in at_clone.items():
+        monkeypatch.setenv(k, v)
+    c = a.clone()
+    assert c.device_bytes() == a.device_bytes()
+    want, want_vad = a.process(x[:, 3:])              # (34 frames: a call the schedule spreads over streams)
+    got, vad = c.process(x[:, 3:])
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)) and np.array_equal(vad.view(np.uint32), want_vad.view(np.uint32))
