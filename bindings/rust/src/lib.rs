@@ -71,6 +71,10 @@ extern "C" {
         hip_stream: *mut c_void,
     ) -> c_int;
     fn nnn_batch_fault(b: *const RawBatch) -> c_int;
+    fn nnn_batch_hold_streams(b: *mut RawBatch, streams: *const c_int, n: c_int) -> c_int;
+    fn nnn_batch_resume_streams(b: *mut RawBatch, streams: *const c_int, n: c_int) -> c_int;
+    fn nnn_batch_num_held(b: *const RawBatch) -> c_int;
+    fn nnn_batch_held_mask(b: *const RawBatch, held: *mut u8, n: usize) -> c_int;
     fn nnn_host_alloc(bytes: usize) -> *mut c_void;
     fn nnn_host_free(p: *mut c_void);
     fn nnn_model_from_rnnoise_text(text: *const u8, len: usize) -> *mut RawModel;
@@ -237,6 +241,29 @@ impl BatchDenoiser {
     /// `nnn_batch_process_device` on their own HIP stream and synchronise that stream themselves.
     pub fn fault(&self) -> bool {
         unsafe { nnn_batch_fault(self.raw) != 0 }
+    }
+
+    /// From the next `process` on the listed streams sit out: their state is parked, their input is not read, their rows of
+    /// `output` and `vad` are left as they were, and no work is done for blocks of streams that are all held
+    /// (`nnn_batch_hold_streams`).  `Err` (nothing changed) on an index out of range, a repeat or a stream already held.
+    pub fn hold_streams(&mut self, streams: &[i32]) -> Result<(), ()> {
+        let rc = unsafe { nnn_batch_hold_streams(self.raw, streams.as_ptr(), streams.len() as c_int) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Held streams take part again from the next `process` on, exactly as if the calls in between had not happened for them.
+    pub fn resume_streams(&mut self, streams: &[i32]) -> Result<(), ()> {
+        let rc = unsafe { nnn_batch_resume_streams(self.raw, streams.as_ptr(), streams.len() as c_int) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    pub fn num_held(&self) -> usize {
+        unsafe { nnn_batch_num_held(self.raw) as usize }
+    }
+    /// `[n_streams]`: which streams are held.
+    pub fn held(&self) -> Vec<bool> {
+        let mut m = vec![0u8; self.n];
+        let rc = unsafe { nnn_batch_held_mask(self.raw, m.as_mut_ptr(), m.len()) };
+        assert_eq!(rc, 0, "nnnoiseless-mi355x: backend error");
+        m.into_iter().map(|v| v != 0).collect()
     }
 
     pub fn reset(&mut self) {

@@ -133,6 +133,46 @@ int nnn_batch_export_streams_device(nnn_batch *b, const int *streams, int n, voi
 int nnn_batch_import_streams_device(nnn_batch *b, const int *streams, int n, const void *d_src, void *hip_stream);
 
 /*
+ * Hold and resume.  A batch advances all its streams in lock-step; a server's calls join, leave, mute and go on hold at different times.
+ * nnn_batch_hold_streams: from the next processing call on, the listed streams do not take part.  nnn_batch_resume_streams: from the next
+ * processing call on they take part again, exactly as if the calls in between had not happened for them -- a stream produces the output
+ * and VAD the reference's DenoiseState produces when process_frame is called only on the frames the stream was live for (a state nobody
+ * calls does not change, src/denoise.rs:95-116).  The server pattern: reset a slot when a call joins (nnn_batch_reset_streams), hold it
+ * when the call goes quiet or on hold, resume it, export it to move it to another batch.
+ * While a stream is held, every processing call (process_device / process_host / process_pcm_device / process_pcm_host, every format,
+ * interleave and discard_first)
+ *   - does not use the stream's input samples: the caller's buffer may hold anything there, NaN included (a host-buffer call may still
+ *     copy those bytes to the device; nothing is computed from them);
+ *   - writes neither the stream's output samples nor its d_vad entries: those bytes of the caller's buffers are left as they were
+ *     (in interleaved PCM: the held channel's samples inside a frame that live channels write);
+ *   - leaves the stream's rows of the frame log (nnn_batch_set_frame_log) and its taps (nnn_batch_read_tap) UNSPECIFIED;
+ *   - changes nothing for the live streams: their bits are those of the same call with nothing held.
+ * Work whose streams are all held is not done: the blocks of a kernel that would serve only held streams return at once (tiles of 64
+ * streams in the high-pass and LPC kernels, runs of 16 in the pitch and RNN kernels, of 4 in the transforms and the synthesis), so a host
+ * that wants idle slots to be free keeps them together.  A held stream beside live ones in such a run costs what a live one costs.
+ * The state of a held stream is its record (the format above), parked in device memory of the batch: NNN_STREAM_STATE_BYTES per stream
+ * of the batch, allocated at the first hold and counted in nnn_batch_device_bytes from then on.  That FIRST hold of a batch is not
+ * asynchronous: it waits for the batch's work, allocates and synchronises the device (a stall for every batch on it); a real-time host
+ * makes an empty hold, nnn_batch_hold_streams(b, NULL, 0), right after creating the batch, which allocates and holds nothing.  From then on both calls are asynchronous and ordered
+ * on the batch's own stream like import and reset (after every call made before, before every call made after); both validate first and
+ * refuse, changing nothing, on: an index outside [0, n_streams), a repeated index, a NULL list, a stream that is already held (hold) or
+ * is not held (resume), and -- hold only, like export -- a batch whose nnn_batch_fault is set.  With no stream held every call behaves,
+ * bit for bit, as it does in a batch that never held one.
+ * How the other calls meet a held stream:
+ *   nnn_batch_export_streams[_device]                  return the parked record (a copy)
+ *   nnn_batch_import_streams[_device], reset_streams   replace the parked record; the stream stays held
+ *   nnn_batch_reset                                    releases every hold
+ *   nnn_batch_clone                                    the clone has the same held set and parked records
+ *   nnn_batch_save_state / nnn_batch_load_state        refused while any stream is held (the raw image has no place for parked records)
+ *   processing calls with EVERY stream held            succeed, advance the frame counter, launch nothing
+ *   host-buffer processing calls                       with any stream held they run in one piece, not in overlapped chunks
+ */
+int nnn_batch_hold_streams(nnn_batch *b, const int *streams, int n);     /* already held: refused */
+int nnn_batch_resume_streams(nnn_batch *b, const int *streams, int n);   /* not held: refused     */
+int nnn_batch_num_held(const nnn_batch *b);
+int nnn_batch_held_mask(const nnn_batch *b, uint8_t *held, size_t n);    /* held[s] = 0 / 1 for s < n_streams; n >= n_streams */
+
+/*
  * n_frames x process_frame for every stream, buffers resident in device memory.
  *   sample i of frame t of stream s:  d_in [s * stream_stride + t * frame_stride + i]   (floats)
  *                                     d_out[s * stream_stride + t * frame_stride + i]   (may alias d_in)

@@ -75,6 +75,11 @@ int nnn_node_synchronize(nnn_node *n);
 int nnn_node_reset_streams(nnn_node *n, const int *streams, int n_list);
 int nnn_node_export_streams(nnn_node *n, const int *streams, int n_list, void *host_dst, size_t dst_bytes);
 int nnn_node_import_streams(nnn_node *n, const int *streams, int n_list, const void *host_src, size_t src_bytes);
+/* Hold and resume by node-global index (nnn_batch_hold_streams / nnn_batch_resume_streams of the shards that own the streams; every
+ * shard's part of the list is checked before any shard is changed).  nnn_node_num_held: held streams over all shards. */
+int nnn_node_hold_streams(nnn_node *n, const int *streams, int n_list);
+int nnn_node_resume_streams(nnn_node *n, const int *streams, int n_list);
+int nnn_node_num_held(const nnn_node *n);
 /* 1 if any shard reports nnn_batch_fault */
 int nnn_node_fault(const nnn_node *n);
 

@@ -171,6 +171,17 @@ class BatchDenoiser {
     {
         check(nnn_batch_import_streams(b_.get(), streams.data(), (int)streams.size(), records.data(), records.size()));
     }
+    // hold and resume (nnn_batch_hold_streams): held streams sit out the processing calls -- state parked, input not read, output and VAD
+    // rows left as they were, no work done for blocks of streams that are all held -- and continue bit for bit when resumed
+    void hold_streams(const std::vector<int> &streams) { check(nnn_batch_hold_streams(b_.get(), streams.data(), (int)streams.size())); }
+    void resume_streams(const std::vector<int> &streams) { check(nnn_batch_resume_streams(b_.get(), streams.data(), (int)streams.size())); }
+    int num_held() const { return nnn_batch_num_held(b_.get()); }
+    std::vector<uint8_t> held() const   // [num_streams()]: 1 = held
+    {
+        std::vector<uint8_t> m((size_t)num_streams());
+        check(nnn_batch_held_mask(b_.get(), m.data(), m.size()));
+        return m;
+    }
     // records in device memory, asynchronous on hip_stream (nullptr: the batch's own stream)
     void export_streams_device(const std::vector<int> &streams, void *d_dst, void *hip_stream = nullptr)
     {

@@ -215,6 +215,28 @@ class BatchDenoiser:
         r = _ffi.stream_records(records, a.size)
         self._lib.check(self._lib.L.nnn_batch_import_streams(self._h, p, a.size, _ffi.ptr(r), r.nbytes))
 
+    def hold_streams(self, idx):
+        """From the next processing call on the listed streams do not take part: their state is parked, their input is not read, their
+        rows of `out` and `vad` are left as they were, and work that would serve only held streams is not done (include/nnn_batch.h
+        nnn_batch_hold_streams).  Enqueued in order with the processing calls; returns at once."""
+        a, p = _ffi.stream_list(idx)
+        self._lib.check(self._lib.L.nnn_batch_hold_streams(self._h, p, a.size))
+
+    def resume_streams(self, idx):
+        """The listed held streams take part again from the next processing call on, exactly as if the calls in between had not
+        happened for them."""
+        a, p = _ffi.stream_list(idx)
+        self._lib.check(self._lib.L.nnn_batch_resume_streams(self._h, p, a.size))
+
+    def held(self):
+        """bool [n_streams]: which streams are held."""
+        m = np.zeros(self.n_streams, np.uint8)
+        self._lib.check(self._lib.L.nnn_batch_held_mask(self._h, _ffi.ptr(m), m.size))
+        return m.astype(bool)
+
+    def num_held(self):
+        return int(self._lib.L.nnn_batch_num_held(self._h))
+
     def export_streams_device(self, idx, d_dst, hip_stream=0):
         """Records into device memory at d_dst (an int, len(idx) * STREAM_STATE_BYTES bytes); asynchronous on hip_stream."""
         a, p = _ffi.stream_list(idx)
@@ -252,17 +274,22 @@ class BatchDenoiser:
         self.frames_done += T
         return out, vad
 
-    def process_pcm(self, x, fmt, channels=1, discard_first=False):
+    def process_pcm(self, x, fmt, channels=1, discard_first=False, out=None, vad=None):
         """Packed PCM in the reference callers' formats, x: [n_groups, n_frames * 480, channels] (int16 for PCM_I16,
         float32 otherwise), n_groups * channels == n_streams.  Returns (out [n_groups, n_out_frames * 480, channels],
-        vad [n_frames, n_streams]); n_out_frames = n_frames - 1 if discard_first drops the first frame after a reset."""
+        vad [n_frames, n_streams]); n_out_frames = n_frames - 1 if discard_first drops the first frame after a reset.  `out` (x's shape
+        and dtype) and `vad`, when handed in, are written in place: what held streams own in them stays as it was."""
         x = np.ascontiguousarray(x, dtype=_ffi.PCM_DTYPE[fmt])
         if x.ndim != 3 or x.shape[2] != channels or x.shape[0] * channels != self.n_streams or x.shape[1] % FRAME_SIZE:
             raise ValueError(f"process_pcm needs x of shape [n_streams / channels, n_frames * {FRAME_SIZE}, channels], got {x.shape}")
         G, N, Cc = x.shape
         T = N // FRAME_SIZE
-        out = np.zeros_like(x)
-        vad = np.empty((T, self.n_streams), np.float32)
+        out = np.zeros_like(x) if out is None else out
+        vad = np.empty((T, self.n_streams), np.float32) if vad is None else vad
+        if not (isinstance(out, np.ndarray) and out.shape == x.shape and out.dtype == x.dtype and out.flags.c_contiguous and out.flags.writeable):
+            raise ValueError("process_pcm: `out` must be a writable C-contiguous array of x's shape and dtype")
+        if not (isinstance(vad, np.ndarray) and vad.shape == (T, self.n_streams) and vad.dtype == np.float32 and vad.flags.c_contiguous and vad.flags.writeable):
+            raise ValueError("process_pcm: `vad` must be a writable C-contiguous float32 array of shape [n_frames, n_streams]")
         L = _ffi.PcmLayout(fmt, channels, int(bool(discard_first)), 0, N * channels, FRAME_SIZE * channels)
         fresh = self.frames_done == 0
         self._lib.check(self._lib.L.nnn_batch_process_pcm_host(self._h, _ffi.ptr(x), _ffi.ptr(out), _ffi.ptr(vad), T, C.byref(L)))

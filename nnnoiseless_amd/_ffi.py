@@ -22,7 +22,7 @@ BATCH_SYMBOLS = [
     "nnn_host_alloc", "nnn_host_free", "nnn_last_error", "nnn_batch_fault", "nnn_batch_debug_withhold_flag", "nnn_batch_set_frame_log",
     "nnn_batch_create_opts", "nnn_batch_max_group_frames", "nnn_batch_device_bytes", "nnn_batch_set_back_end", "nnn_device_local_cpulist",
     "nnn_batch_reset_streams", "nnn_batch_export_streams", "nnn_batch_import_streams", "nnn_batch_export_streams_device",
-    "nnn_batch_import_streams_device",
+    "nnn_batch_import_streams_device", "nnn_batch_hold_streams", "nnn_batch_resume_streams", "nnn_batch_num_held", "nnn_batch_held_mask",
 ]
 TRAIN_SYMBOLS = [
     "nnn_train_create", "nnn_train_destroy", "nnn_train_reset", "nnn_train_process_device", "nnn_train_process_host",
@@ -35,6 +35,7 @@ NODE_SYMBOLS = [
     "nnn_node_create", "nnn_node_destroy", "nnn_node_num_streams", "nnn_node_num_shards", "nnn_node_shard", "nnn_node_batch", "nnn_node_reset",
     "nnn_node_process_host", "nnn_node_process_pcm_host", "nnn_node_process_device", "nnn_node_process_device_streams", "nnn_node_synchronize",
     "nnn_node_fault", "nnn_node_shard_cpus", "nnn_node_reset_streams", "nnn_node_export_streams", "nnn_node_import_streams",
+    "nnn_node_hold_streams", "nnn_node_resume_streams", "nnn_node_num_held",
 ]
 RNNOISE_SYMBOLS = [
     "rnnoise_get_frame_size", "rnnoise_get_size", "rnnoise_init", "rnnoise_create", "rnnoise_destroy",
@@ -148,6 +149,17 @@ class Library:
             L.nnn_batch_import_streams.argtypes = [vp, ip, i32, vp, sz]
             L.nnn_batch_export_streams_device.argtypes = [vp, ip, i32, vp, vp]
             L.nnn_batch_import_streams_device.argtypes = [vp, ip, i32, vp, vp]
+        if hasattr(L, "nnn_batch_hold_streams"):
+            ip = C.POINTER(i32)
+            L.nnn_batch_hold_streams.argtypes = [vp, ip, i32]
+            L.nnn_batch_resume_streams.argtypes = [vp, ip, i32]
+            L.nnn_batch_num_held.argtypes = [vp]
+            L.nnn_batch_held_mask.argtypes = [vp, vp, sz]
+        if hasattr(L, "nnn_node_hold_streams"):
+            ip = C.POINTER(i32)
+            L.nnn_node_hold_streams.argtypes = [vp, ip, i32]
+            L.nnn_node_resume_streams.argtypes = [vp, ip, i32]
+            L.nnn_node_num_held.argtypes = [vp]
         if hasattr(L, "nnn_node_reset_streams"):
             ip = C.POINTER(i32)
             L.nnn_node_reset_streams.argtypes = [vp, ip, i32]

@@ -380,7 +380,8 @@ __device__ __forceinline__ void bk_dense(const LayerDesc &L, const BkRnn &R, con
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct BkActs { int dense, vad, noise, dn, out, vo; };   // activation kinds of the model at hand (ref: src/rnn.rs:242-250)
 // XR: the fused kernel of a one-frame call whose X transform rode in k_pitch's launch (transform_inputs, xt_rider).
-template <bool FUSED, class SH, bool XR = false>
+// HELD: some stream of the batch is held (nnn_batch_hold_streams) -- the instantiation that looks at the live mask; the launch plan picks it.
+template <bool FUSED, class SH, bool XR = false, bool HELD = false>
 __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0, BkActs acts, const uint4 *__restrict__ Wq,
                                               const float *__restrict__ fpar, int tile0, int g)
 {
@@ -398,7 +399,9 @@ __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0,
     tile += tile0;                                 // tile0: first tile of this model's run
     const int r0 = sub * BK_ROWS;                  // first row of the tile handled here
     if (tile * TILE + r0 >= b.S) return;   // (a block whose streams are all padding -- the last tile of a batch that is not a multiple of 64 -- has nothing to do)
+    if (HELD && !live_any(b, tile, r0, BK_ROWS)) return;   // (... or all held, nnn_batch_hold_streams: the rider blocks of these streams returned too, xt_rider)
     const int sl = r0 + wave0, s = tile * TILE + sl;   // this wave's stream: its row in the tile, its index in the batch
+    const int s_out = (HELD && !live_stream(b, tile, sl)) ? b.S_pad : s;   // (a held stream writes no audio, VAD or frame log: a padding stream's index, see k_synth)
     // ---- LDS
     float *tab = (float *)(lds + o.tab);
     int *live = (int *)(lds + o.live), *flagw = (int *)(lds + o.flag) + wave0;
@@ -578,7 +581,7 @@ __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0,
         {
             const float b_graw = lane < NB ? gout[wave * BK_GW + lane] : 0.0f, b_g = lane < NB ? gout[wave * BK_GW + 24 + lane] : 0.0f;
             float4 smq[2];   // (the overlap memory: read and written inside, per frame)
-            synth_frame<true>(b, sp, f, tile, sl, s, lane, t, Z, part, K.X, K.P, K.ex, K.ep, K.xn, b_graw, b_g, vadl[wave], !silent, sm, smq);
+            synth_frame<true>(b, sp, f, tile, sl, s_out, lane, t, Z, part, K.X, K.P, K.ex, K.ep, K.xn, b_graw, b_g, vadl[wave], !silent, sm, smq);
         }
         NNN_STAMP(b, 12);
     }

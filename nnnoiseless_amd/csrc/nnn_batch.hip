@@ -175,6 +175,8 @@ struct GroupPlan {
     int g = 0;                     // frames
     BackEnd back = BACK_UNFUSED;
     int hp = 0;                    // 0 = k_hp, 1 / 2 = k_hp2<1> / k_hp2<2>
+    bool held = false;             // some stream is held (nnn_batch_hold_streams): the high-pass, pitch and back-end kernels in the instantiations that
+                                   // look at the live mask (and feed held streams zeros); otherwise the code a batch without a mask runs
     bool head = false;             // k_hp2 also runs the LPC sums' head (and k_pitch<true> takes it)
     bool lpc_in_pitch = false;     // k_pitch<true> does the LPC analysis
     int lpc_fc = 0;                // otherwise: k_lpc with lpc_fc frames per wave behind the high-pass, 0 = k_lpc_wide (lpc_launch)
@@ -273,7 +275,15 @@ struct nnn_batch {
     bool ss_idx_busy = false;
     char *ss_stage = nullptr;          // the host variants' records on the device (grow-only)
     size_t ss_stage_cap = 0;
+    // held streams (nnn_batch_hold_streams), made on the first hold and counted in device_bytes
+    unsigned *park = nullptr;          // device: the parked record of every stream, [S][NNN_STREAM_STATE_BYTES / 4]; valid while the stream is held
+    unsigned long long *live = nullptr;   // device: Buffers::live of every scratch set's argument block
+    std::vector<uint8_t> held;         // the host's copy of the mask, for checking arguments and for the host-buffer calls' copies back
+    int n_held = 0;
 };
+
+static int hold_prepare(nnn_batch *h);
+static int hold_release_all(nnn_batch *h);
 
 template <class T> static hipError_t dalloc(nnn_batch *h, T **p, size_t count, bool is_state)
 {
@@ -598,6 +608,9 @@ static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *g
     HIPCHK(hipFuncSetAttribute((const void *)k_back<true, BkShapeBuiltin>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
     HIPCHK(hipFuncSetAttribute((const void *)k_back<false, BkShapeBuiltin>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
     HIPCHK(hipFuncSetAttribute((const void *)k_back<true, BkShapeBuiltin, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+    HIPCHK(hipFuncSetAttribute((const void *)k_back<true, BkShapeBuiltin, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+    HIPCHK(hipFuncSetAttribute((const void *)k_back<false, BkShapeBuiltin, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+    HIPCHK(hipFuncSetAttribute((const void *)k_back<true, BkShapeBuiltin, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
     HIPCHK(hipDeviceSynchronize());
     h->id = g_next_batch_id.fetch_add(1) & 0xFFFFFu;
     if (!h->id) h->id = g_next_batch_id.fetch_add(1) & 0xFFFFFu;
@@ -705,6 +718,7 @@ extern "C" int nnn_batch_reset(nnn_batch *h)
     if (!h) return fail("null batch");
     if (int rc = quiesce(h)) return rc;
     for (auto &sb : h->state_bufs) HIPCHK(hipMemset(sb.first, 0, sb.second));
+    if (int rc = hold_release_all(h)) return rc;   // (every hold is released: a fresh batch holds nothing)
     HIPCHK(hipDeviceSynchronize());
     *h->fault_host = 0;
     h->frame_count = 0;
@@ -732,6 +746,7 @@ extern "C" int nnn_batch_save_state(nnn_batch *h, void *host_dst, size_t dst_byt
     if (!h || !host_dst) return fail("null argument");
     const size_t need = nnn_batch_state_bytes(h);
     if (dst_bytes < need) return fail("state buffer too small: %zu bytes needed", need);
+    if (h->n_held) return fail("nnn_batch_save_state refused: %d streams are held (nnn_batch_hold_streams) and the raw state image has no place for their parked records; resume or export them first", h->n_held);
     if (int rc = quiesce(h)) return rc;
     SnapHeader hd{kSnapMagic, h->frame_count, h->group_count, (uint64_t)h->state_bufs.size(), (uint64_t)need, (uint64_t)h->S};
     char *p = (char *)host_dst;
@@ -754,6 +769,7 @@ extern "C" int nnn_batch_load_state(nnn_batch *h, const void *host_src, size_t s
     memcpy(&hd, host_src, sizeof(hd));
     if (hd.magic != kSnapMagic || hd.n_bufs != h->state_bufs.size() || hd.total != need || hd.streams != (uint64_t)h->S || src_bytes < need)
         return fail("state snapshot does not match this batch (streams / models / max_group_frames / library build)");
+    if (h->n_held) return fail("nnn_batch_load_state refused: %d streams are held (nnn_batch_hold_streams) and the raw state image has no place for their parked records; resume them or nnn_batch_reset first", h->n_held);
     if (int rc = quiesce(h)) return rc;
     const char *p = (const char *)host_src + sizeof(hd);
     for (auto &sb : h->state_bufs) {
@@ -786,6 +802,19 @@ extern "C" nnn_batch *nnn_batch_clone(nnn_batch *h)
         nnn_batch_destroy(c);
         fail("state copy failed");
         return nullptr;
+    }
+    if (h->n_held) {   // the same held set and parked records
+        ok = hold_prepare(c) == 0 &&
+             hipMemcpy(c->park, h->park, (size_t)h->S * NNN_STREAM_STATE_BYTES, hipMemcpyDeviceToDevice) == hipSuccess &&
+             hipMemcpy(c->live, h->live, (size_t)h->NT * sizeof(unsigned long long), hipMemcpyDeviceToDevice) == hipSuccess &&
+             hipDeviceSynchronize() == hipSuccess;
+        if (!ok) {
+            nnn_batch_destroy(c);
+            fail("copy of the parked records failed");
+            return nullptr;
+        }
+        c->held = h->held;
+        c->n_held = h->n_held;
     }
     c->frame_count = h->frame_count;
     c->group_count = h->group_count;
@@ -831,7 +860,23 @@ struct SsArgs {
     int dec_row0;       // decimated-ring row of the first value of frame frame_count - 3
     int slot_next;      // ring slot of frame frame_count
     const int *flag;    // device import: != 0 = the record check refused the list (nothing is written)
+    // hold / resume (nnn_batch_hold_streams): the records are the batch's own parked ones, record of stream s at index s, and the kernel
+    // that moves a stream's state also flips its bit of the live mask
+    int by_stream;      // mode 1 / 2: the record of entry i is record ss_stream(i), not record i (mode 0: the caller offsets the pointer)
+    int live_op;        // 0 = leave the mask alone, 1 = clear the listed streams' bits (hold), 2 = set them (resume)
+    unsigned long long *live;
 };
+// bits of one tile's live word: a plain vector atomic (the launches of a batch are ordered, the streams of a list may share a word)
+__device__ __forceinline__ void ss_live_bits(const SsArgs &a, int tile, unsigned long long bits)
+{
+#ifdef __HIPCC__
+    if (a.live_op == 1) atomicAnd(a.live + tile, ~bits);
+    else atomicOr(a.live + tile, bits);
+#else   // (the tests' interpreter runs one thread at a time)
+    if (a.live_op == 1) a.live[tile] &= ~bits;
+    else a.live[tile] |= bits;
+#endif
+}
 __device__ __forceinline__ int ss_stream(const SsArgs &a, int i) { return a.mode == 0 ? a.first + i : (a.mode == 1 ? a.small[i] : a.idx[i]); }
 
 // the 32-bit word of TI row r (record order: mem_id, last_period, last_gain, mem_hp_x[0..1], ceps_mem[8][22], lastg[22]) of a stream
@@ -922,15 +967,17 @@ __device__ __forceinline__ void ss_derived(const Buffers &b, const SsArgs &a, in
 __global__ void __launch_bounds__(256) k_ss_export_streams(Buffers b, SsArgs a, unsigned *dst)
 {
     const int i = blockIdx.x, s = ss_stream(a, i), dims = a.dims[s / TILE];
-    unsigned *rec = dst + (size_t)i * SS_WORDS;
+    unsigned *rec = dst + (size_t)(a.by_stream ? s : i) * SS_WORDS;
     for (int j = threadIdx.x; j < SS_WORDS; j += 256) rec[j] = ss_export_word(b, a, s, j, dims);
+    if (a.live_op && threadIdx.x == 0) ss_live_bits(a, s / TILE, 1ull << (s % TILE));
 }
 // src = nullptr: the zero record (reset)
 __global__ void __launch_bounds__(256) k_ss_import_streams(Buffers b, SsArgs a, const unsigned *src)
 {
     if (a.flag && a.flag[0]) return;
     const int i = blockIdx.x, s = ss_stream(a, i), dims = a.dims[s / TILE], tile = s / TILE, lane = s % TILE;
-    const unsigned *rec = src ? src + (size_t)i * SS_WORDS : nullptr;
+    const unsigned *rec = src ? src + (size_t)(a.by_stream ? s : i) * SS_WORDS : nullptr;
+    if (a.live_op && threadIdx.x == 0) ss_live_bits(a, tile, 1ull << lane);
     for (int j = threadIdx.x; j < SS_WORDS; j += 256) {
         const unsigned v = rec ? rec[j] : 0u;
         const int r = ss_ti_row(j);
@@ -947,6 +994,13 @@ __global__ void __launch_bounds__(256) k_ss_import_streams(Buffers b, SsArgs a, 
 
 // A contiguous run of streams (a migration, a whole batch): one block per tile, lane = stream on the TI rows (one 256-byte row per wave
 // instruction), the record's TI words transposed through LDS; the stream-major parts are contiguous runs of the record either way.
+// the bits of the streams of `tile` that a contiguous list (mode 0) names
+__device__ __forceinline__ unsigned long long ss_tile_bits(const SsArgs &a, int tile)
+{
+    const int lo = a.first > tile * TILE ? a.first - tile * TILE : 0, hi = a.first + a.n < (tile + 1) * TILE ? a.first + a.n - tile * TILE : TILE;
+    const unsigned long long upto = hi >= TILE ? ~0ull : (1ull << hi) - 1ull;
+    return upto & ~((1ull << lo) - 1ull);
+}
 __global__ void __launch_bounds__(256) k_ss_export_tiles(Buffers b, SsArgs a, unsigned *dst)
 {
     __shared__ unsigned T[SS_TI_ROWS][TILE + 1];
@@ -963,6 +1017,7 @@ __global__ void __launch_bounds__(256) k_ss_export_tiles(Buffers b, SsArgs a, un
             rec[j] = r >= 0 ? T[r][q] : ss_export_word(b, a, s, j, dims);
         }
     }
+    if (a.live_op && tid == 0) ss_live_bits(a, tile, ss_tile_bits(a, tile));
 }
 __global__ void __launch_bounds__(256) k_ss_import_tiles(Buffers b, SsArgs a, const unsigned *src)
 {
@@ -971,6 +1026,7 @@ __global__ void __launch_bounds__(256) k_ss_import_tiles(Buffers b, SsArgs a, co
     if (a.flag && a.flag[0]) return;
     const int tile = a.first / TILE + (int)blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int dims = a.dims[tile];
+    if (a.live_op && tid == 0) ss_live_bits(a, tile, ss_tile_bits(a, tile));
     const int s_me = tile * TILE + lane;
     const bool mine = s_me >= a.first && s_me < a.first + a.n;   // (lane = stream)
     auto rec_of = [&](int q) { return src + (size_t)(tile * TILE + q - a.first) * SS_WORDS; };
@@ -1024,6 +1080,22 @@ __global__ void __launch_bounds__(256) k_ss_check(SsArgs a, const unsigned *src,
     }
 }
 
+// The listed streams that are held keep their state in the parked record, not in the batch: an export's record comes from there
+// (to_records), an import's or a reset's (src = nullptr: the zero record) goes there.  Runs behind the ordinary kernel of the call, which
+// has read or written the held streams' dead batch state to no effect.
+__global__ void __launch_bounds__(256) k_ss_parked(SsArgs a, const unsigned long long *live, unsigned *park, int to_records, unsigned *recs, const unsigned *src)
+{
+    if (a.flag && a.flag[0]) return;
+    const int i = blockIdx.x, s = ss_stream(a, i), dims = a.dims[s / TILE];
+    if ((live[s / TILE] >> (s % TILE)) & 1ull) return;
+    unsigned *slab = park + (size_t)s * SS_WORDS;
+    for (int j = threadIdx.x; j < SS_WORDS; j += 256) {
+        if (to_records) recs[(size_t)i * SS_WORDS + j] = slab[j];
+        else if (src) slab[j] = src[(size_t)i * SS_WORDS + j];
+        else slab[j] = j == 0 ? NNN_STREAM_STATE_MAGIC : j == 1 ? NNN_STREAM_STATE_VERSION : j == 2 ? NNN_STREAM_STATE_BYTES : j < 6 ? (unsigned)((dims >> (8 * (j - 3))) & 255) : 0u;
+    }
+}
+
 static void ss_dims_host(const nnn_batch *h, int s, int d[3])
 {
     for (const nnn_batch::ModelGroup &G : h->groups)
@@ -1035,7 +1107,7 @@ static void ss_dims_host(const nnn_batch *h, int s, int d[3])
         }
     d[0] = d[1] = d[2] = -1;
 }
-enum SsOp { SS_RESET = 0, SS_EXPORT = 1, SS_IMPORT = 2 };
+enum SsOp { SS_RESET = 0, SS_EXPORT = 1, SS_IMPORT = 2, SS_HOLD = 3, SS_RESUME = 4 };
 // Everything a call can check on the host, before it writes anything.  host_rec: an import's records in host memory (checked here),
 // or nullptr.  Also used by the node (nnn_node.cpp) to check every shard's part of a list before any shard is written.
 int nnn_batch_check_streams(const nnn_batch *h, int op, const int *streams, int n, const void *host_rec, size_t bytes, bool need_buf)
@@ -1044,6 +1116,7 @@ int nnn_batch_check_streams(const nnn_batch *h, int op, const int *streams, int 
     if (n < 0) return fail("negative stream count");
     if (n > 0 && !streams) return fail("null stream list");
     if (op == SS_EXPORT && nnn_batch_fault(h)) return fail("export refused: the batch is faulted (nnn_batch_fault); its state is invalid");
+    if (op == SS_HOLD && nnn_batch_fault(h)) return fail("hold refused: the batch is faulted (nnn_batch_fault); its state is invalid");
     if (need_buf && n > 0 && !host_rec) return fail("null record buffer");
     if (need_buf && bytes < (size_t)n * NNN_STREAM_STATE_BYTES)
         return fail("record buffer too small: %zu bytes for %d records of %d", bytes, n, NNN_STREAM_STATE_BYTES);
@@ -1055,6 +1128,9 @@ int nnn_batch_check_streams(const nnn_batch *h, int op, const int *streams, int 
             if (seen[(size_t)s]) return fail("stream %d listed twice", s);
             seen[(size_t)s] = 1;
         }
+        const bool is_held = h->n_held > 0 && h->held[(size_t)s];
+        if (op == SS_HOLD && is_held) return fail("stream %d (entry %d) is already held", s, i);
+        if (op == SS_RESUME && !is_held) return fail("stream %d (entry %d) is not held", s, i);
     }
     if (op == SS_IMPORT && host_rec)
         for (int i = 0; i < n; i++) {
@@ -1204,6 +1280,11 @@ static int ss_call(nnn_batch *h, SsOp op, const int *streams, int n, const void 
     }
     if (op == SS_EXPORT) ss_launch(h, true, a, tiles, nullptr, host_dst ? (void *)h->ss_stage : d_dst, st);
     else ss_launch(h, false, a, tiles, op == SS_RESET ? nullptr : d_src, nullptr, st);
+    bool any_held = false;
+    for (int i = 0; i < n && h->n_held > 0 && !any_held; i++) any_held = h->held[(size_t)streams[i]] != 0;
+    if (any_held)
+        hipLaunchKernelGGL(k_ss_parked, dim3((unsigned)n), dim3(256), 0, st, a, (const unsigned long long *)h->live, h->park, op == SS_EXPORT ? 1 : 0,
+                           (unsigned *)(host_dst ? (void *)h->ss_stage : d_dst), (const unsigned *)(op == SS_IMPORT ? d_src : nullptr));
     if (host_dst) HIPCHK(hipMemcpyAsync(host_dst, h->ss_stage, bytes, hipMemcpyDeviceToHost, st));
     if (int rc = ss_end(h, st)) return rc;
     if (host_src || host_dst) HIPCHK(hipStreamSynchronize(st));
@@ -1236,6 +1317,80 @@ extern "C" int nnn_batch_import_streams_device(nnn_batch *h, const int *streams,
     if (int rc = nnn_batch_check_streams(h, SS_IMPORT, streams, n, nullptr, 0, false)) return rc;
     if (n > 0 && (!d_src || ((uintptr_t)d_src & 3))) return fail("null or unaligned record buffer");
     return ss_call(h, SS_IMPORT, streams, n, nullptr, nullptr, d_src, nullptr, hip_stream, true);
+}
+
+// ---- hold and resume (include/nnn_batch.h) ---------------------------------------------------------------------
+// Hold = the export above into the batch's own parked records, resume = the import from them (which re-phases the history into the ring
+// slots the frame counter of NOW reads); the same launch flips the streams' bits of the live mask the processing kernels look at.
+static std::vector<unsigned long long> live_all(const nnn_batch *h)
+{
+    std::vector<unsigned long long> w((size_t)h->NT, ~0ull);
+    if (h->S % TILE) w.back() = (1ull << (h->S % TILE)) - 1ull;   // (padding streams are never live)
+    return w;
+}
+static int hold_prepare(nnn_batch *h)
+{
+    if (h->park) return 0;
+    NNN_RT_LOCK;
+    if (int rc = quiesce(h)) return rc;
+    unsigned *park = nullptr;
+    unsigned long long *live = nullptr;
+    HIPCHK(dalloc(h, &park, (size_t)h->S * SS_WORDS, false));
+    HIPCHK(dalloc(h, &live, (size_t)h->NT, false));
+    const std::vector<unsigned long long> w = live_all(h);
+    HIPCHK(hipMemcpy(live, w.data(), w.size() * sizeof(w[0]), hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    h->park = park;
+    h->live = live;
+    h->held.assign((size_t)h->S, 0);
+    h->n_held = 0;
+    for (int set = 0; set < NSET; set++) h->b[set].live = live;   // (every argument block, the ones a later nnn_batch_set_taps re-derives included)
+    return 0;
+}
+static int hold_call(nnn_batch *h, bool hold, const int *streams, int n)
+{
+    if (int rc = nnn_batch_check_streams(h, hold ? SS_HOLD : SS_RESUME, streams, n, nullptr, 0, false)) return rc;
+    // (the first hold of a batch allocates the parked records and the mask, which waits for the device: a host that cannot stall at its
+    // first mute makes an empty hold -- n = 0 -- when it creates the batch)
+    if (n == 0 && !hold) return 0;
+    if (int rc = ss_prepare(h)) return rc;
+    if (int rc = hold_prepare(h)) return rc;
+    if (n == 0) return 0;
+    bool ok = true;
+    hipStream_t st = ss_begin(h, nullptr, ok);
+    if (!ok) return fail("could not order the call after the batch's earlier work: %s", hipGetErrorString(hipGetLastError()));
+    SsArgs a;
+    bool tiles = false;
+    if (int rc = ss_args(h, streams, n, st, a, tiles)) return rc;
+    a.by_stream = 1;
+    a.live_op = hold ? 1 : 2;
+    a.live = h->live;
+    unsigned *rec0 = h->park + (tiles ? (size_t)a.first * SS_WORDS : 0);   // (the tile kernels count records from the list's first stream)
+    ss_launch(h, hold, a, tiles, rec0, rec0, st);
+    // (the launch is enqueued and will flip the device's bits: the host's copy follows it whatever the bookkeeping below reports)
+    for (int i = 0; i < n; i++) h->held[(size_t)streams[i]] = hold ? 1 : 0;
+    h->n_held += hold ? n : -n;
+    return ss_end(h, st);
+}
+extern "C" int nnn_batch_hold_streams(nnn_batch *h, const int *streams, int n) { return hold_call(h, true, streams, n); }
+extern "C" int nnn_batch_resume_streams(nnn_batch *h, const int *streams, int n) { return hold_call(h, false, streams, n); }
+extern "C" int nnn_batch_num_held(const nnn_batch *h) { return h ? h->n_held : 0; }
+extern "C" int nnn_batch_held_mask(const nnn_batch *h, uint8_t *held, size_t n)
+{
+    if (!h || !held) return fail("null argument");
+    if (n < (size_t)h->S) return fail("mask buffer too small: %d entries needed", h->S);
+    for (int s = 0; s < h->S; s++) held[s] = h->n_held > 0 ? h->held[(size_t)s] : 0;
+    return 0;
+}
+// nnn_batch_reset: every stream takes part again
+static int hold_release_all(nnn_batch *h)
+{
+    if (!h->live) return 0;
+    const std::vector<unsigned long long> w = live_all(h);
+    HIPCHK(hipMemcpy(h->live, w.data(), w.size() * sizeof(w[0]), hipMemcpyHostToDevice));
+    h->held.assign((size_t)h->S, 0);
+    h->n_held = 0;
+    return 0;
 }
 
 // ---- one group of frames ------------------------------------------------------------------------
@@ -1305,6 +1460,7 @@ static void plan_group(const nnn_batch *h, int g, GroupPlan &p)
     // k_hp on two waves per tile (recurrence | everything else, k_hp2): for launches that leave SIMDs empty; groups: two tiles per block
     const bool split = k.hp_split >= 0 ? k.hp_split != 0 : h->NT <= 256;
     p.hp = !split ? 0 : ((k.hp_tpb ? k.hp_tpb == 2 : (g > 1 && h->NT >= 8)) ? 2 : 1);
+    p.held = h->n_held > 0;   // (the host's copy of the mask is as the device's will be when the launch runs: hold and resume are enqueued in call order)
     // One-frame groups of batches whose pitch launch is a single round of workgroups (two 8-wave blocks per compute unit) run the LPC
     // analysis inside k_pitch: one launch fewer on the critical path of a real-time tick (measured per one-frame call: -6 us at 4096
     // streams, level at 8192, +9 us at 16 384).  With k_hp2, the part of its sums that needs none of the new frame rides in the
@@ -1341,10 +1497,10 @@ static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, cons
     case ST_HP:
         // (`fill`: this is the first launch of a call whose parameter table is k_hp's to fill, see k_hp)
         if (p.hp == 2)
-            L.go(K_HP, k_hp2<2>, dim3((NT + 1) / 2 + (p.head ? (5 * NT + 3) / 4 : 0)), dim3(256), 0, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0, p.head ? 1 : 0);
+            L.go(K_HP, p.held ? k_hp2<2, true> : k_hp2<2, false>, dim3((NT + 1) / 2 + (p.head ? (5 * NT + 3) / 4 : 0)), dim3(256), 0, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0, p.head ? 1 : 0);
         else if (p.hp == 1)
-            L.go(K_HP, k_hp2<1>, dim3(NT + (p.head ? (5 * NT + 1) / 2 : 0)), dim3(128), 0, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0, p.head ? 1 : 0);
-        else L.go(K_HP, k_hp, dim3(NT), dim3(64), 0, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0);
+            L.go(K_HP, p.held ? k_hp2<1, true> : k_hp2<1, false>, dim3(NT + (p.head ? (5 * NT + 1) / 2 : 0)), dim3(128), 0, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0, p.head ? 1 : 0);
+        else L.go(K_HP, p.held ? k_hp<true> : k_hp<false>, dim3(NT), dim3(64), 0, b, sp0, g, call ? *call : StepParams{}, call ? fill : 0);
         if (p.lpc_in_pitch) break;   // (k_pitch does it on its way, see there)
         if (!p.lpc_fc) L.go(K_LPC, k_lpc_wide, dim3(NT * ug), dim3(320), 0, b, sp0, g);
         else L.go(K_LPC, k_lpc, dim3(NT * ((ug + p.lpc_fc - 1) / p.lpc_fc)), dim3(64), 0, b, sp0, g, p.lpc_fc);
@@ -1354,9 +1510,9 @@ static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, cons
         const int chain = p.chain ? 1 : 0, seq0 = (int)(h->frame_count & 0x3fffffffu) + 1;
         const unsigned grid = Sp / PK_SPB * (chain ? ug : 1u);
         if (p.lpc_in_pitch)
-            L.go(K_PITCH, k_pitch<true>, dim3(grid + (p.riders ? Sp / 8 : 0u)), dim3(PK_T), 0, b, sp0, g, chain, seq0, h->tickets, p.head ? 2 : 1, p.riders ? (int)grid : 0);
+            L.go(K_PITCH, p.held ? k_pitch<true, true> : k_pitch<true, false>, dim3(grid + (p.riders ? Sp / 8 : 0u)), dim3(PK_T), 0, b, sp0, g, chain, seq0, h->tickets, p.head ? 2 : 1, p.riders ? (int)grid : 0);
         else
-            L.go(K_PITCH, k_pitch<false>, dim3(grid + (p.riders ? Sp / 8 : 0u)), dim3(PK_T), 0, b, sp0, g, chain, seq0, h->tickets, 0, p.riders ? (int)grid : 0);
+            L.go(K_PITCH, p.held ? k_pitch<false, true> : k_pitch<false, false>, dim3(grid + (p.riders ? Sp / 8 : 0u)), dim3(PK_T), 0, b, sp0, g, chain, seq0, h->tickets, 0, p.riders ? (int)grid : 0);
         if (chain) h->tickets += grid;   // (launches of one batch's pitch stage are ordered among themselves: a stateful stage)
         break;
     }
@@ -1364,9 +1520,9 @@ static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, cons
         if (p.back == BACK_FUSED) {   // the fused back end takes the place of this stage and the two behind it: one launch per resident model
             for (const nnn_batch::ModelGroup &G : h->groups) {
                 if (p.riders)   // (its X transform done by k_pitch's rider blocks, see xt_rider)
-                    L.go(K_BACK, k_back<true, BkShapeBuiltin, true>, dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.back_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
+                    L.go(K_BACK, p.held ? k_back<true, BkShapeBuiltin, true, true> : k_back<true, BkShapeBuiltin, true, false>, dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.back_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
                 else
-                    L.go(K_BACK, k_back<true, BkShapeBuiltin>, dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.back_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
+                    L.go(K_BACK, p.held ? k_back<true, BkShapeBuiltin, false, true> : k_back<true, BkShapeBuiltin, false, false>, dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.back_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
             }
             break;
         }
@@ -1377,7 +1533,7 @@ static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, cons
         for (size_t i = 0; i < h->groups.size(); i++) {   // one launch per resident model (a run of whole tiles)
             const nnn_batch::ModelGroup &G = h->groups[i];
             if (p.rnn[i] == RK_BACK)
-                L.go(K_RNN, k_back<false, BkShapeBuiltin>, dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.rnn16_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
+                L.go(K_RNN, p.held ? k_back<false, BkShapeBuiltin, false, true> : k_back<false, BkShapeBuiltin, false, false>, dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.rnn16_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
             else if (p.rnn[i] == RK_WF_BUILTIN)
                 L.go(K_RNN, k_rnn_wf<BkShapeBuiltin>, dim3((unsigned)(G.ntiles * (TILE / WF_ROWS))), dim3(64 * WF_WAVES), G.wf_lds, b, G.plan, G.wp,
                      G.wq, G.fpar, G.tile0, g);
@@ -1418,6 +1574,7 @@ struct CallPlan {             // what a call decides before it launches anything
     bool pipe;                // spread over the internal streams (otherwise the groups' stages back to back on the caller's stream)
     int sched, lanes;         // the schedule of a pipelined call
     bool fold_fill, early_hp, hp_after;   // see plan_call
+    bool idle;                // every stream is held (nnn_batch_hold_streams): the call moves the frame counter and launches nothing
 };
 static CallPlan plan_call(const nnn_batch *h, int n_frames, hipStream_t st)
 {
@@ -1439,7 +1596,8 @@ static CallPlan plan_call(const nnn_batch *h, int n_frames, hipStream_t st)
     // -0.3), 32 768 x 96 lanes 2 +1.9 % (stages +0.4), 32 768 x 48 stages +1.0 % (lanes 2: -0.4): one stream per stage for calls of two
     // groups, two lanes for longer ones.  Costs the second block of scratch sets and the longer ring (650 against 360 KB per stream).
     const bool auto_big = k.sched_auto && h->S_pad > AUTO_BIG;
-    c.pipe = k.use_pipeline && k.sched != SCHED_SEQ && !h->profiling && n_frames >= PIPE_MIN && !(auto_big && h->depth < 2);
+    c.idle = h->n_held == h->S;
+    c.pipe = !c.idle && k.use_pipeline && k.sched != SCHED_SEQ && !h->profiling && n_frames >= PIPE_MIN && !(auto_big && h->depth < 2);
     if (c.pipe) {
         int n = 2;
         while ((n_frames + n - 1) / n > h->gmax) n += 2;
@@ -1453,7 +1611,7 @@ static CallPlan plan_call(const nnn_batch *h, int n_frames, hipStream_t st)
     c.lanes = auto_big ? 2 : k.n_lanes;
     // the per-frame parameter table: a launch of its own ahead of a pipelined call's streams; otherwise the call's first kernel (k_hp of
     // the first group) fills it on its way (a one-frame call is a handful of launches of 15-35 us: one fewer is 4 % of it)
-    c.fold_fill = !c.pipe && !h->profiling;
+    c.fold_fill = (!c.pipe && !h->profiling) || c.idle;   // (idle: no table at all)
     // The next call's high-pass chain may start before this stream has seen the previous call drain, when the caller has
     // promised that inputs are final at call time (nnn_batch_set_inputs_ready): it depends on the previous call only through
     // its own stream (biquad state) and the history-ring slots it overwrites (synthesis events of the groups that read them).
@@ -1551,7 +1709,7 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
         for (int k = 0, t = 0; k < n_groups; k++) {
             const int g = cp.sizes[k], set0 = (int)(h->group_count % h->depth) * h->gmax;
             plan_group(h, g, h->plan);
-            for (int s = 0; s < ST_COUNT; s++) launch_stage(h, s, set0, h->plan, tab + t, st, h->profiling, plain_out, (cp.fold_fill && k == 0) ? &v0 : nullptr, n_frames);
+            for (int s = 0; s < ST_COUNT && !cp.idle; s++) launch_stage(h, s, set0, h->plan, tab + t, st, h->profiling, plain_out, (cp.fold_fill && k == 0) ? &v0 : nullptr, n_frames);
             h->group_count += 1;
             h->frame_count += g;
             h->last_set = set0 + g - 1;
@@ -1740,6 +1898,33 @@ static int process_host_chunked(nnn_batch *h, const char *in, char *out, float *
     return nnn_batch_synchronize(h);   // (also reports a frame hand-off that never arrived)
 }
 
+// The copies back of the host-buffer calls: the frames the call wrote, from a host image `src` of the device buffer into the caller's.
+// A held stream's samples and VAD entries are not the call's to write (nnn_batch_hold_streams): the caller's bytes stay as they were,
+// per channel where held and live channels share an interleaved group.
+static void host_frames_back(const nnn_batch *h, char *out, const char *src, const nnn_pcm_layout *L, int n_out)
+{
+    const size_t e = (size_t)pcm_elem_bytes(L->format), ch = (size_t)L->channels, groups = (size_t)h->S / ch, fr = (size_t)FRAME * ch * e;
+    for (size_t g = 0; g < groups; g++) {
+        size_t n_live = ch;
+        for (size_t c = 0; c < ch && h->n_held > 0; c++) n_live -= h->held[g * ch + c] ? 1 : 0;
+        if (!n_live) continue;
+        for (int t = 0; t < n_out; t++) {
+            const size_t o = g * L->group_stride * e + (size_t)t * L->frame_stride * e;
+            if (n_live == ch) { memcpy(out + o, src + o, fr); continue; }
+            for (size_t c = 0; c < ch; c++)
+                if (!h->held[g * ch + c])
+                    for (size_t i = 0; i < (size_t)FRAME; i++) memcpy(out + o + (i * ch + c) * e, src + o + (i * ch + c) * e, e);
+        }
+    }
+}
+static void host_vad_back(const nnn_batch *h, float *vad, const float *src, int n_frames)
+{
+    if (!h->n_held) { memcpy(vad, src, (size_t)n_frames * h->S * sizeof(float)); return; }
+    for (int t = 0; t < n_frames; t++)
+        for (int s = 0; s < h->S; s++)
+            if (!h->held[(size_t)s]) vad[(size_t)t * h->S + s] = src[(size_t)t * h->S + s];
+}
+
 // Host buffers: ship the bounding span of the (possibly strided) layout, run, bring the written frames back.
 static int process_host_span_impl(nnn_batch *h, const void *in, void *out, float *vad, int n_frames, const nnn_pcm_layout *L);
 static int process_host_span(nnn_batch *h, const void *in, void *out, float *vad, int n_frames, const nnn_pcm_layout *L)
@@ -1778,12 +1963,8 @@ static int process_host_span_impl(nnn_batch *h, const void *in, void *out, float
         if (!rc) rc = nnn_batch_synchronize(h);   // (also reports a frame hand-off that never arrived)
         else hipStreamSynchronize(h->stream);
         if (!rc) {
-            for (size_t g = 0; g < groups; g++)
-                for (int t = 0; t < n_frames - drop; t++) {
-                    size_t o = g * L->group_stride * e + (size_t)t * L->frame_stride * e;
-                    memcpy((char *)out + o, h->zc_host + o, fr);
-                }
-            if (vad) memcpy(vad, h->zc_host + vofs, vbytes);
+            host_frames_back(h, (char *)out, h->zc_host, L, n_frames - drop);
+            if (vad) host_vad_back(h, vad, (const float *)(h->zc_host + vofs), n_frames);
         }
         return rc;
     }
@@ -1825,7 +2006,9 @@ static int process_host_span_impl(nnn_batch *h, const void *in, void *out, float
         while (chunk < HC && (size_t)chunk * fr * groups < ((size_t)1 << 20)) chunk *= 2;
         if ((size_t)chunk * fr * groups < ((size_t)1 << 20)) chunk = 0;
     }
-    if (chunk > 0 && n_frames > chunk && L->frame_stride == (size_t)FRAME * L->channels)
+    // (the chunks' downloads go straight into the caller's buffers, whole rows of every stream: with streams held the call takes the
+    // one-piece path below, whose copy back leaves out what a held stream owns)
+    if (chunk > 0 && n_frames > chunk && L->frame_stride == (size_t)FRAME * L->channels && !h->n_held)
         return process_host_chunked(h, (const char *)in, (char *)out, vad, n_frames, L, d, dv, drop, chunk);
     hipError_t err = hipMemcpyAsync(d, in, span, hipMemcpyHostToDevice, h->stream);
     int rc = 0;
@@ -1834,16 +2017,16 @@ static int process_host_span_impl(nnn_batch *h, const void *in, void *out, float
     if (!rc) {
         // `out` may alias `in` and may be strided: bring the span back and copy only real frames
         std::vector<char> &tmp = h->stage_host;
-        if (tmp.size() < span) tmp.resize(span);
+        const bool vad_masked = vad && h->n_held > 0;   // (the VAD rows through the host image too: a held stream's entries are not copied)
+        const size_t vofs = (span + 15) / 16 * 16;
+        if (tmp.size() < vofs + (vad_masked ? vbytes : 0)) tmp.resize(vofs + (vad_masked ? vbytes : 0));
         err = hipMemcpyAsync(tmp.data(), d, span, hipMemcpyDeviceToHost, h->stream);
-        if (err == hipSuccess && vad) err = hipMemcpyAsync(vad, dv, vbytes, hipMemcpyDeviceToHost, h->stream);
+        if (err == hipSuccess && vad) err = hipMemcpyAsync(vad_masked ? (void *)(tmp.data() + vofs) : (void *)vad, dv, vbytes, hipMemcpyDeviceToHost, h->stream);
         if (err == hipSuccess) err = hipStreamSynchronize(h->stream);
-        if (err == hipSuccess)
-            for (size_t g = 0; g < groups; g++)
-                for (int t = 0; t < n_frames - drop; t++) {
-                    size_t o = g * L->group_stride * e + (size_t)t * L->frame_stride * e;
-                    memcpy((char *)out + o, tmp.data() + o, fr);
-                }
+        if (err == hipSuccess) {
+            host_frames_back(h, (char *)out, tmp.data(), L, n_frames - drop);
+            if (vad_masked) host_vad_back(h, vad, (const float *)(tmp.data() + vofs), n_frames);
+        }
         if (err != hipSuccess) rc = fail("copy back failed: %s", hipGetErrorString(err));
         if (!rc) rc = nnn_batch_synchronize(h);   // (also reports a frame hand-off that never arrived)
     } else {
@@ -2157,7 +2340,7 @@ static void enqueue_feature_group(nnn_batch *h, hipStream_t st, const float *in,
     v.log = nullptr;
     v.log_frames = 0;
     hipLaunchKernelGGL(k_fill_params, dim3(1), dim3(64), 0, st, sp, v, g, h->nslot);
-    hipLaunchKernelGGL(k_hp, dim3(NT), dim3(64), 0, st, b, (const StepParams *)sp, g, StepParams{}, 0);
+    hipLaunchKernelGGL(k_hp<false>, dim3(NT), dim3(64), 0, st, b, (const StepParams *)sp, g, StepParams{}, 0);
     if (full) {
         const int fc = lpc_launch(h, g);
         if (!fc) hipLaunchKernelGGL(k_lpc_wide, dim3(NT * ug), dim3(320), 0, st, b, (const StepParams *)sp, g);

@@ -203,8 +203,26 @@ __device__ __forceinline__ void hp_recurrence(const float (&xs)[HP_CH], float (&
     }
 }
 
-template <int FMT, bool VEC>
-__device__ __forceinline__ void hp_frame(const Buffers &b, const char *sp_in, long long sp_group_stride, int slot, int ch, int tile, int lane, HpState &st, float *Ly)
+// A held stream in a tile that still has live ones runs along on zeros: nothing of the caller's buffer enters its (dead) state.
+// MUTE is an instantiation of the high-pass KERNELS (k_hp<true>, k_hp2<.., true>), which the launch plan picks for calls made while some
+// stream is held; it also carries the kernels' whole-tile returns.  A batch that holds nothing runs the instructions it ran before there
+// was a mask: the recurrence is a serial chain bound by issue, and a one-frame tick is three such latency-bound launches, where even the
+// compiled-in presence of a never-taken mask check moved the code enough to measure (1 us of 110).  The kernels of the tick -- these,
+// k_pitch and k_back -- therefore take the mask as a template flag (HELD there), the others as a run-time null pointer.
+// The filter's state goes to zero with them: the stream's history is exact zeros from its first held chunk on (digital silence, the
+// cheapest thing every later kernel knows), not the biquad's tail dying away through ever smaller values -- which keeps the coarse pitch
+// search of the stream's whole block off its certified path for as long as it lasts (measured: scattered held streams +10 % per call).
+__device__ __forceinline__ void hp_mute(float (&xs)[HP_CH], float &m0, float &m1, bool held)
+{
+#pragma unroll
+    for (int j = 0; j < HP_CH; j++) xs[j] = held ? 0.0f : xs[j];
+    m0 = held ? 0.0f : m0;
+    m1 = held ? 0.0f : m1;
+}
+
+template <int FMT, bool VEC, bool MUTE>
+__device__ __forceinline__ void hp_frame(const Buffers &b, const char *sp_in, long long sp_group_stride, int slot, int ch, int tile, int lane, HpState &st, float *Ly,
+                                         bool held)
 {
     const int elem = pcm_elem_bytes(FMT), sstride = ch * elem;
     const int s = tile * TILE + lane;
@@ -235,7 +253,10 @@ __device__ __forceinline__ void hp_frame(const Buffers &b, const char *sp_in, lo
     float ys[HP_CH], dvs[HP_CH / 2];
     for (int c = 0; c <= FRAME / HP_CH; c++) {
         float xs[HP_CH];
-        if (c < FRAME / HP_CH) nxt.get(xs);
+        if (c < FRAME / HP_CH) {
+            nxt.get(xs);
+            if (MUTE) hp_mute(xs, m0, m1, held);
+        }
         if (c > 0) {
 #pragma unroll
             for (int t = 0; t < HP_CH / 2; t++) dec[(size_t)(HP_CH / 2 * (c - 1) + t) * TILE] = dvs[t];
@@ -292,17 +313,18 @@ __device__ __forceinline__ StepParams step_params_at(const StepParams &v, int t,
 // `fill` > 0: this launch is the first of a call of `fill` frames whose table nobody has filled -- a launch of its own for that costs
 // a one-frame call 6 of its 150 us -- so block 0 writes it (for the kernels behind this one, which start when this one is done) and
 // every block takes its own frames' entries from the call's parameters `v0`; the group's first frame is entry `t0` of the call.
-template <int FMT, bool VEC>
+template <int FMT, bool VEC, bool MUTE>
 __device__ __forceinline__ void hp_group(const Buffers &b, const StepParams *sp, int g, int tile, int lane, float *Ly, const StepParams &v0, int fill)
 {
     float *hp = NNN_TI(b.hp_mem, 2, tile, lane);
     float *hl = NNN_TI(b.hp_last, 1, tile, lane);
     HpState st{hp[0], hp[TILE], hl[0]};
+    const bool held = MUTE && !live_stream(b, tile, lane);
     for (int f = 0; f < g; f++) {
         // (what a frame needs of its table entry: where its input starts and which ring slot takes it)
         const char *in = fill > 0 ? v0.in + (long long)f * v0.frame_stride : sp[f].in;
         const int slot = fill > 0 ? (v0.slot + f) % b.nslot : sp[f].slot;
-        hp_frame<FMT, VEC>(b, in, fill > 0 ? v0.group_stride : sp[f].group_stride, slot, fill > 0 ? v0.channels : sp[f].channels, tile, lane, st, Ly);
+        hp_frame<FMT, VEC, MUTE>(b, in, fill > 0 ? v0.group_stride : sp[f].group_stride, slot, fill > 0 ? v0.channels : sp[f].channels, tile, lane, st, Ly, held);
     }
     hp[0] = st.m0;
     hp[TILE] = st.m1;
@@ -342,8 +364,9 @@ __device__ __forceinline__ float lpc_head_chain(const float *base, float x0)
 // stores per chunk, the decimation -- used to stand between one chunk's recurrence and the next (0.5 of every 1.3 us).  Here wave 0
 // runs loads and recurrence only and leaves each chunk's results in one of two LDS buffers; wave 1 (another SIMD) takes them from there
 // behind one block barrier per chunk and does the rest while wave 0 is a chunk further.  Same arithmetic, same bits.
-template <int FMT, bool VEC>
-__device__ __forceinline__ void hp_chain_frame(const Buffers &b, const char *sp_in, long long sp_group_stride, int ch, int tile, int lane, float &m0, float &m1, float *Ly2, int &k)
+template <int FMT, bool VEC, bool MUTE>
+__device__ __forceinline__ void hp_chain_frame(const Buffers &b, const char *sp_in, long long sp_group_stride, int ch, int tile, int lane, float &m0, float &m1, float *Ly2, int &k,
+                                               bool held)
 {
     const int elem = pcm_elem_bytes(FMT), sstride = ch * elem;
     const int s = tile * TILE + lane;
@@ -354,6 +377,7 @@ __device__ __forceinline__ void hp_chain_frame(const Buffers &b, const char *sp_
     for (int c = 0; c < FRAME / HP_CH; c++, k++) {
         float xs[HP_CH], ys[HP_CH];
         nxt.get(xs);
+        if (MUTE) hp_mute(xs, m0, m1, held);
         if (c + 1 < FRAME / HP_CH) nxt.load(in + (long long)(c + 1) * HP_CH * sstride, sstride);
         hp_recurrence(xs, ys, m0, m1);
         float *L = Ly2 + (k & 1) * (TILE * HP_LD) + lane * HP_LD;
@@ -399,15 +423,16 @@ __device__ __forceinline__ void hp_store_frame(const Buffers &b, int slot, int t
         if (slot == 0 && c == 0) h[ring_len(nslot)] = ys[0];
     }
 }
-template <int FMT, bool VEC>
+template <int FMT, bool VEC, bool MUTE>
 __device__ __forceinline__ void hp_chain_group(const Buffers &b, const StepParams *sp, int g, int tile, int lane, float *Ly2, const StepParams &v0, int fill)
 {
     float *hp = NNN_TI(b.hp_mem, 2, tile, lane);
     float m0 = hp[0], m1 = hp[TILE];
     int k = 0;
+    const bool held = MUTE && !live_stream(b, tile, lane);
     for (int f = 0; f < g; f++) {
         const char *in = fill > 0 ? v0.in + (long long)f * v0.frame_stride : sp[f].in;
-        hp_chain_frame<FMT, VEC>(b, in, fill > 0 ? v0.group_stride : sp[f].group_stride, fill > 0 ? v0.channels : sp[f].channels, tile, lane, m0, m1, Ly2, k);
+        hp_chain_frame<FMT, VEC, MUTE>(b, in, fill > 0 ? v0.group_stride : sp[f].group_stride, fill > 0 ? v0.channels : sp[f].channels, tile, lane, m0, m1, Ly2, k, held);
     }
     hp[0] = m0;
     hp[TILE] = m1;
@@ -428,12 +453,16 @@ __device__ __forceinline__ void hp_chain_group(const Buffers &b, const StepParam
 // way.  NNN_HP_EXTERN: this unit only declares them; NNN_ONLY_HP: this unit is nnn_hp.hip and defines nothing else.  A build that
 // defines neither (the tests' interpreter, scripts/build_variant.sh, the stamp builds) holds everything in one unit, as before.
 #ifdef NNN_HP_EXTERN
-template <int TPB> __global__ void k_hp2(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
-extern template __global__ void k_hp2<1>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
-extern template __global__ void k_hp2<2>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
-__global__ void k_hp(Buffers b, const StepParams *sp, int g, StepParams v0, int fill);
+template <int TPB, bool MUTE> __global__ void k_hp2(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
+template <bool MUTE> __global__ void k_hp(Buffers b, const StepParams *sp, int g, StepParams v0, int fill);
+extern template __global__ void k_hp2<1, false>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
+extern template __global__ void k_hp2<2, false>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
+extern template __global__ void k_hp2<1, true>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
+extern template __global__ void k_hp2<2, true>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
+extern template __global__ void k_hp<false>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill);
+extern template __global__ void k_hp<true>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill);
 #else
-template <int TPB>
+template <int TPB, bool MUTE>
 __global__ void __launch_bounds__(128 * TPB) k_hp2(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head)
 {
     static_assert(HP_CH == 32, "");
@@ -443,6 +472,7 @@ __global__ void __launch_bounds__(128 * TPB) k_hp2(Buffers b, const StepParams *
         const int item = 2 * TPB * ((int)blockIdx.x - nblk) + wave;
         if (!head || item >= 5 * b.NT) return;
         const int tile = item / 5, lag = item - 5 * tile, nslot = b.nslot;
+        if (MUTE && live_word(b, tile) == 0ull) return;   // (every stream of the tile held: its pitch blocks, which would take these sums, return too)
         const int slot = fill > 0 ? v0.slot : sp->slot;
         const float *h = b.hist + (size_t)(tile * TILE + lane) * hist_stride(nslot);
         const int rb = ring_base(slot, nslot);
@@ -460,13 +490,23 @@ __global__ void __launch_bounds__(128 * TPB) k_hp2(Buffers b, const StepParams *
     const int tile = (int)blockIdx.x * TPB + (wave - role * TPB);
     __shared__ float Ly2s[TPB][2 * TILE * HP_LD];
     float *Ly2 = Ly2s[wave - role * TPB];
-    if (tile >= b.NT) {   // (a ragged last block: its spare waves only keep the barrier count)
+    // (the parameter table is tile 0's to fill whether or not its streams take part)
+    if (role == 1 && fill > 0 && tile == 0)
+        for (int t = lane; t < fill; t += 64) ((StepParams *)sp)[t] = step_params_at(v0, t, b.nslot);
+    if (MUTE) {   // a block none of whose tiles has a live stream (nnn_batch_hold_streams) returns at once
+        bool any = false;
+#pragma unroll
+        for (int u = 0; u < TPB; u++) {
+            const int tu = (int)blockIdx.x * TPB + u;
+            any = any || (tu < b.NT && live_word(b, tu) != 0ull);
+        }
+        if (!any) return;
+    }
+    if (tile >= b.NT || (MUTE && live_word(b, tile) == 0ull)) {   // (a ragged last block, a held tile beside a live one: the spare waves only keep the barrier count)
         for (int i = 0; i < g * (FRAME / HP_CH); i++) __syncthreads();
         return;
     }
     if (role == 1) {
-        if (fill > 0 && tile == 0)
-            for (int t = lane; t < fill; t += 64) ((StepParams *)sp)[t] = step_params_at(v0, t, b.nslot);
         float *hl = NNN_TI(b.hp_last, 1, tile, lane);
         float prev = hl[0];
         int k = 0;
@@ -478,29 +518,35 @@ __global__ void __launch_bounds__(128 * TPB) k_hp2(Buffers b, const StepParams *
     wf_setprio_high();
     const StepParams &lay = fill > 0 ? v0 : *sp;
     const bool vec = lay.channels == 1 && ((((size_t)lay.in) | (size_t)lay.group_stride | (size_t)lay.frame_stride) & 15) == 0;
-    if (fmt == PCM_F32) { if (vec) hp_chain_group<PCM_F32, true>(b, sp, g, tile, lane, Ly2, v0, fill); else hp_chain_group<PCM_F32, false>(b, sp, g, tile, lane, Ly2, v0, fill); }
-    else if (fmt == PCM_I16) { if (vec) hp_chain_group<PCM_I16, true>(b, sp, g, tile, lane, Ly2, v0, fill); else hp_chain_group<PCM_I16, false>(b, sp, g, tile, lane, Ly2, v0, fill); }
-    else { if (vec) hp_chain_group<PCM_F32_UNIT, true>(b, sp, g, tile, lane, Ly2, v0, fill); else hp_chain_group<PCM_F32_UNIT, false>(b, sp, g, tile, lane, Ly2, v0, fill); }
+    if (fmt == PCM_F32) { if (vec) hp_chain_group<PCM_F32, true, MUTE>(b, sp, g, tile, lane, Ly2, v0, fill); else hp_chain_group<PCM_F32, false, MUTE>(b, sp, g, tile, lane, Ly2, v0, fill); }
+    else if (fmt == PCM_I16) { if (vec) hp_chain_group<PCM_I16, true, MUTE>(b, sp, g, tile, lane, Ly2, v0, fill); else hp_chain_group<PCM_I16, false, MUTE>(b, sp, g, tile, lane, Ly2, v0, fill); }
+    else { if (vec) hp_chain_group<PCM_F32_UNIT, true, MUTE>(b, sp, g, tile, lane, Ly2, v0, fill); else hp_chain_group<PCM_F32_UNIT, false, MUTE>(b, sp, g, tile, lane, Ly2, v0, fill); }
 }
 
+template <bool MUTE>
 __global__ void __launch_bounds__(64, HP_CH <= 16 ? 3 : 1) k_hp(Buffers b, const StepParams *sp, int g, StepParams v0, int fill)
 {
     const int lane = threadIdx.x, tile = blockIdx.x;
     if (fill > 0 && tile == 0)
         for (int t = lane; t < fill; t += 64) ((StepParams *)sp)[t] = step_params_at(v0, t, b.nslot);
+    if (MUTE && live_word(b, tile) == 0ull) return;   // (every stream of the tile held, nnn_batch_hold_streams)
     const int fmt = fill > 0 ? v0.fmt : sp->fmt;
     wf_setprio_high();   // a lone wave on a serial chain that shares its SIMD with another kernel's wave (+1 % at 4096 streams)
     const StepParams &lay = fill > 0 ? v0 : *sp;
     const bool vec = lay.channels == 1 && ((((size_t)lay.in) | (size_t)lay.group_stride | (size_t)lay.frame_stride) & 15) == 0;
     __shared__ float Ly[TILE * HP_LD];
-    if (fmt == PCM_F32) { if (vec) hp_group<PCM_F32, true>(b, sp, g, tile, lane, Ly, v0, fill); else hp_group<PCM_F32, false>(b, sp, g, tile, lane, Ly, v0, fill); }
-    else if (fmt == PCM_I16) { if (vec) hp_group<PCM_I16, true>(b, sp, g, tile, lane, Ly, v0, fill); else hp_group<PCM_I16, false>(b, sp, g, tile, lane, Ly, v0, fill); }
-    else { if (vec) hp_group<PCM_F32_UNIT, true>(b, sp, g, tile, lane, Ly, v0, fill); else hp_group<PCM_F32_UNIT, false>(b, sp, g, tile, lane, Ly, v0, fill); }
+    if (fmt == PCM_F32) { if (vec) hp_group<PCM_F32, true, MUTE>(b, sp, g, tile, lane, Ly, v0, fill); else hp_group<PCM_F32, false, MUTE>(b, sp, g, tile, lane, Ly, v0, fill); }
+    else if (fmt == PCM_I16) { if (vec) hp_group<PCM_I16, true, MUTE>(b, sp, g, tile, lane, Ly, v0, fill); else hp_group<PCM_I16, false, MUTE>(b, sp, g, tile, lane, Ly, v0, fill); }
+    else { if (vec) hp_group<PCM_F32_UNIT, true, MUTE>(b, sp, g, tile, lane, Ly, v0, fill); else hp_group<PCM_F32_UNIT, false, MUTE>(b, sp, g, tile, lane, Ly, v0, fill); }
 }
 
 #ifdef NNN_ONLY_HP
-template __global__ void k_hp2<1>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
-template __global__ void k_hp2<2>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
+template __global__ void k_hp2<1, false>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
+template __global__ void k_hp2<2, false>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
+template __global__ void k_hp2<1, true>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
+template __global__ void k_hp2<2, true>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill, int head);
+template __global__ void k_hp<false>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill);
+template __global__ void k_hp<true>(Buffers b, const StepParams *sp, int g, StepParams v0, int fill);
 #endif
 #endif   // NNN_HP_EXTERN
 
@@ -667,6 +713,7 @@ __global__ void __launch_bounds__(64) k_lpc(Buffers b, const StepParams *sp0, in
     // t mod 8, where k_hp's block t wrote the ring.
     int tile, chunk, sub_;
     xcd_tile_block_units((int)blockIdx.x, b.NT, 1, nch, chunk, tile, sub_);
+    if (live_word(b, tile) == 0ull) return;   // (every stream of the tile held, nnn_batch_hold_streams: k_hp wrote nothing for it, k_pitch reads nothing)
     const int f0 = chunk * fc, nf = g - f0 < fc ? g - f0 : fc;
     const int nslot = b.nslot, ring = dec_ring_len(nslot);
     int slot[LPC_FC];
@@ -748,6 +795,7 @@ __global__ void __launch_bounds__(320) k_lpc_wide(Buffers b, const StepParams *s
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int tile, f, sub_;
     xcd_tile_block_units((int)blockIdx.x, b.NT, 1, g, f, tile, sub_);
+    if (live_word(b, tile) == 0ull) return;   // (every stream of the tile held, as in k_lpc)
     const int slot = sp0[f].slot;
     const float *base = b.dec + ((size_t)tile * dec_len(b.nslot) + (size_t)dec_base(slot, b.nslot)) * TILE + lane;
     const float x0 = NNN_TI(b.xlp0, b.nslot, tile, lane)[(size_t)slot * TILE];   // x_lp[0] is special (ref: src/pitch.rs:458)
@@ -1256,7 +1304,7 @@ static_assert(PK_SEG_F1 % 2 == 0 && PK_SEG_F1 <= PK_FINE_K, "");
 
 
 // (defined behind the transforms, further down: the X transform of a one-frame call in rider blocks of k_pitch's launch)
-__device__ __forceinline__ void xt_rider(const Buffers &b, const StepParams *sp, int rb, void *lds);
+template <bool HELD> __device__ __forceinline__ void xt_rider(const Buffers &b, const StepParams *sp, int rb, void *lds);
 
 #ifndef NNN_PK_MINWAVES
 #define NNN_PK_MINWAVES 4   // waves per SIMD: two blocks of 8 waves per CU, <= 128 registers
@@ -1276,14 +1324,14 @@ __device__ __forceinline__ void xt_rider(const Buffers &b, const StepParams *sp,
 // 14.5 us launch plus its gap on the call's critical path.  Same sums in the same order: bit-identical to k_lpc / k_lpc_wide.
 // LPC: the instantiation that can run the LPC analysis (`lpc_here`): its autocorrelation holds 36 registers beside the prefetched window, which
 // costs the frame loop of the groups' instantiation spills at the kernel's 128-register limit (round 6).
-template <bool LPC>
+template <bool LPC, bool HELD = false>
 __global__ void __launch_bounds__(PK_T, NNN_PK_MINWAVES) k_pitch(Buffers b, const StepParams *sp0, int g, int chain, int seq0, unsigned tbase, int lpc_here_,
                                                                  int riders)
 {
     __shared__ PkLds L;
     const int lpc_here = LPC ? lpc_here_ : 0;
     if (riders > 0 && (int)blockIdx.x >= riders) {   // (one-frame launches only: chain == 0, the pitch blocks are blocks 0 .. riders - 1)
-        xt_rider(b, sp0, (int)blockIdx.x - riders, &L);
+        xt_rider<HELD>(b, sp0, (int)blockIdx.x - riders, &L);
         return;
     }
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane0 = threadIdx.x & 63;
@@ -1304,6 +1352,12 @@ __global__ void __launch_bounds__(PK_T, NNN_PK_MINWAVES) k_pitch(Buffers b, cons
     xcd_tile_block(item - f_begin * per, b.NT, TILE / PK_SPB, tile, sub_);
     const int q0 = sub_ * PK_SPB;   // first stream of this block within its tile
     if (tile * TILE + q0 >= b.S) return;   // (a block whose streams are all padding -- the last tile of a batch that is not a multiple of 64 -- has nothing to do)
+    // ... or all held (nnn_batch_hold_streams).  The mask is constant for a call: the blocks of these streams return in every frame of a
+    // chained launch -- each after taking its ticket -- so none is ever waited for
+    // (the block's sixteen bits of the tile's word as one 16-bit load: the 64-bit shift and mask cost the one-frame instantiation, which sits at
+    // its register limit, four more spilled registers)
+    static_assert(PK_SPB == 16, "the block's bits of the tile's word are read as one little-endian 16-bit value");
+    if (HELD && b.live && ((const unsigned short *)b.live)[tile * (TILE / PK_SPB) + sub_] == 0) return;
     const int min_period = PITCH_MIN / 2, max_period = PITCH_MAX / 2;
     const bool dec_lane = wave == 0 && lane0 < PK_SPB;                // lane = stream decisions
     int last_period = 0;
@@ -2744,6 +2798,7 @@ __global__ void __launch_bounds__(64 * FFT_SPB, NNN_FFT_MINWAVES) k_fft_xp(Buffe
     int frame, tile, sub;
     fft_block(b, g, frame, tile, sub);
     if (tile * TILE + sub * FFT_SPB >= b.S) return;   // (a block whose streams are all padding -- the last tile of a batch that is not a multiple of 64 -- has nothing to do)
+    if (!live_any(b, tile, sub * FFT_SPB, FFT_SPB)) return;   // (... or all held, nnn_batch_hold_streams)
     b = frame_view(b, frame);
     const int wave = threadIdx.x >> 6;
     transform_inputs<true>(b, sp + frame, tile, sub, t, Z[wave], part[wave]);
@@ -2754,12 +2809,13 @@ __global__ void __launch_bounds__(64 * FFT_SPB, NNN_FFT_MINWAVES) k_fft_xp(Buffe
 // compute unit and bound by their own latency chains, leave most issue slots free.  The fused back end then fetches X instead of
 // computing it (k_back<.., XR>).  The code is k_fft_x's; `lds` is the pitch kernel's own LDS block, which a rider block has to itself.
 struct XtLds { FftLds t; float2 Z[8][NFFT_BUF]; float part[8][4]; };
-__device__ __forceinline__ void xt_rider(const Buffers &b, const StepParams *sp, int rb, void *lds)
+template <bool HELD> __device__ __forceinline__ void xt_rider(const Buffers &b, const StepParams *sp, int rb, void *lds)
 {
     static_assert(sizeof(XtLds) <= sizeof(PkLds) && PK_T == 512 && FFT_SPB == 4, "");
     XtLds &x = *(XtLds *)lds;
     const int wave = threadIdx.x >> 6;
     if ((rb >> 3) * TILE + 8 * (rb & 7) >= b.S) return;
+    if (HELD && !live_any(b, rb >> 3, 16 * ((rb & 7) >> 1), 16)) return;   // (by the sixteen streams of the k_back block that fetches this X: both run or neither)
     transform_inputs<false>(b, sp, rb >> 3, 2 * (rb & 7), x.t, x.Z[wave], x.part[wave]);   // rows 8 (rb % 8) + wave of tile rb / 8
 }
 
@@ -3316,6 +3372,10 @@ __global__ void __launch_bounds__(64 * RNN_WAVES) k_rnn(Buffers b, RnnPlan pl, c
     tile += tile0;                                         // tile0: first tile of this model's run
     const int r0 = sub * rm;                               // first row of the tile handled here
     if (tile * TILE + r0 >= b.S) return;   // (a block whose streams are all padding -- the last tile of a batch that is not a multiple of 64 -- has nothing to do)
+    // (... or all held, nnn_batch_hold_streams.  A block with live rows also runs its held rows, whose feature rows k_fft_xp -- which returns
+    // by four streams -- may not have written in this call: stale or creation-time zeros.  Rows never mix here -- each GEMM row is its own
+    // input row times the shared weights, the live flags are per row -- and a held row's results go to its own dead state.  DESIGN.md section 13.)
+    if (!live_any(b, tile, r0, rm)) return;
     const bool rowl = lane < rm;                           // lane = stream phases: this lane has a row
     const int trow = r0 + (rowl ? lane : 0);               // its row in the tile
     // ---- LDS carve-up (rnn_lds_bytes on the host mirrors it)
@@ -3737,6 +3797,7 @@ __global__ void __launch_bounds__(64 * WF_WAVES, NNN_WF_MINWAVES) k_rnn_wf(Buffe
     tile += tile0;
     const int r0 = sub * rm;                                 // first row of the tile handled here
     if (tile * TILE + r0 >= b.S) return;   // (a block whose streams are all padding -- the last tile of a batch that is not a multiple of 64 -- has nothing to do)
+    if (!live_any(b, tile, r0, rm)) return;   // (... or all held, nnn_batch_hold_streams; held rows beside live ones: see k_rnn)
     const bool rowl = lane0 < rm;
     const int trow = r0 + (rowl ? lane0 : 0);
     NNN_STAMP(b, 50);
@@ -4139,6 +4200,7 @@ __global__ void __launch_bounds__(64 * FFT_SPB, NNN_SYN_MINWAVES) k_synth(Buffer
     int tile, sub;
     xcd_tile_block((int)blockIdx.x, b.NT, TILE / FFT_SPB, tile, sub);
     if (tile * TILE + sub * FFT_SPB >= b.S) return;   // (a block whose streams are all padding -- the last tile of a batch that is not a multiple of 64 -- has nothing to do)
+    if (!live_any(b, tile, sub * FFT_SPB, FFT_SPB)) return;   // (... or all held, nnn_batch_hold_streams)
     const int lane0 = threadIdx.x & 63, sl = sub * FFT_SPB + wave, s = tile * TILE + sl;
     int lane = lane0;
     fft_tables_load(t, b, true);
@@ -4155,6 +4217,9 @@ __global__ void __launch_bounds__(64 * FFT_SPB, NNN_SYN_MINWAVES) k_synth(Buffer
         bc.band[u] = on ? (int)t.band[on ? k : 0] : -1;
         bc.frac[u] = on ? t.frac[bsk(on ? k : 0)] : 0.0f;
     }
+    // (a held stream beside live ones, nnn_batch_hold_streams, is handed to the frame body under a padding stream's index: like one, it
+    // writes neither audio nor VAD nor frame log, and the caller's bytes stay as they were.  The mask is constant for the call.)
+    const int s_out = live_stream(b, tile, sl) ? s : b.S_pad;
     for (int f = 0; f < g; f++) {
         lane = launder_v(lane0);   // keep the frame loop's addresses inside the loop (see launder_v)
         const size_t fo = (size_t)b.S_pad * (size_t)f;   // this frame's scratch set
@@ -4174,7 +4239,7 @@ __global__ void __launch_bounds__(64 * FFT_SPB, NNN_SYN_MINWAVES) k_synth(Buffer
             b_g = NNN_TIF(b, g, NB, f, tile, sl)[(size_t)lane * TILE];
         }
         const float vadv = NNN_TIF(b, vad, 1, f, tile, sl)[0];
-        synth_frame<false, PLAIN>(b, sp0 + f, f, tile, sl, s, lane, t, A, r, Xr, Pr, b_ex, b_ep, b_xp, b_graw, b_g, vadv, live, sm, smq, &bc);
+        synth_frame<false, PLAIN>(b, sp0 + f, f, tile, sl, s_out, lane, t, A, r, Xr, Pr, b_ex, b_ep, b_xp, b_graw, b_g, vadv, live, sm, smq, &bc);
     }
 #pragma unroll
     for (int u = 0; u < 2; u++)

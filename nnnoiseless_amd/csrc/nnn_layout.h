@@ -149,7 +149,19 @@ struct Buffers {
     float wnorm;
     int S, S_pad, NT;
     int taps;                // != 0: kernels also store the quantities only parity tests look at (xc1, xc2, P from bin 400 up)
+    const unsigned long long *live;   // [NT] one word per tile, bit i = stream i of the tile takes part in processing calls (cleared by
+                             //      nnn_batch_hold_streams, set again by nnn_batch_resume_streams; padding streams: 0).  Null -- a batch
+                             //      that never held a stream, the training rows -- means every stream is live.  Constant for a whole call.
 };
+
+// The live mask.  A block asks once, with a block-uniform tile: one word, a uniform branch.
+__device__ __forceinline__ unsigned long long live_word(const Buffers &b, int tile) { return b.live ? b.live[tile] : ~0ull; }
+// any live stream among streams first .. first + n - 1 of the tile (n <= 64)
+__device__ __forceinline__ bool live_any(const Buffers &b, int tile, int first, int n)
+{
+    return ((live_word(b, tile) >> first) & (n >= 64 ? ~0ull : (1ull << n) - 1ull)) != 0ull;
+}
+__device__ __forceinline__ bool live_stream(const Buffers &b, int tile, int sl) { return ((live_word(b, tile) >> sl) & 1ull) != 0ull; }
 
 // Per-frame scratch of set f lies f * S_pad * LEN elements after set 0 in every scratch array, so a launch that covers
 // several consecutive frames (block index = frame * blocks_per_frame + block) reaches its frame's set by offsetting.

@@ -256,7 +256,16 @@ static void spread_vad(nnn_node *n, float *vad, int n_frames)
     if (!vad) return;
     for (auto &s : n->shards) {
         const size_t cnt = (size_t)(s.hi - s.lo);
-        for (int t = 0; t < n_frames; t++) memcpy(vad + (size_t)t * n->n_streams + s.lo, s.vad.data() + (size_t)t * cnt, cnt * sizeof(float));
+        if (nnn_batch_num_held(s.b) == 0) {
+            for (int t = 0; t < n_frames; t++) memcpy(vad + (size_t)t * n->n_streams + s.lo, s.vad.data() + (size_t)t * cnt, cnt * sizeof(float));
+            continue;
+        }
+        // (a held stream's entries are not the call's to write, nnn_batch_hold_streams: the caller's values stay)
+        std::vector<uint8_t> held(cnt);
+        nnn_batch_held_mask(s.b, held.data(), cnt);
+        for (int t = 0; t < n_frames; t++)
+            for (size_t i = 0; i < cnt; i++)
+                if (!held[i]) vad[(size_t)t * n->n_streams + s.lo + i] = s.vad[(size_t)t * cnt + i];
     }
 }
 
@@ -330,7 +339,7 @@ extern "C" int nnn_node_fault(const nnn_node *n)
 // The list is split by shard (part k: the shard-local indices, and where each entry sits in the caller's list); every part is checked on
 // its shard before any shard is written.
 int nnn_batch_check_streams(const nnn_batch *h, int op, const int *streams, int n, const void *host_rec, size_t bytes, bool need_buf);   // nnn_batch.hip
-enum { NODE_SS_RESET = 0, NODE_SS_EXPORT = 1, NODE_SS_IMPORT = 2 };   // (nnn_batch.hip's SsOp)
+enum { NODE_SS_RESET = 0, NODE_SS_EXPORT = 1, NODE_SS_IMPORT = 2, NODE_SS_HOLD = 3, NODE_SS_RESUME = 4 };   // (nnn_batch.hip's SsOp)
 static int node_split(const nnn_node *n, const int *streams, int n_list, std::vector<std::vector<int>> &local, std::vector<std::vector<int>> &at)
 {
     if (!n) return nnn_set_error("null node");
@@ -402,4 +411,27 @@ extern "C" int nnn_node_import_streams(nnn_node *n, const int *streams, int n_li
         if (!local[k].empty())
             if (int rc = nnn_batch_import_streams(n->shards[k].b, local[k].data(), (int)local[k].size(), parts[k].data(), parts[k].size())) return rc;
     return 0;
+}
+
+// hold / resume by node-global index (nnn_batch_hold_streams): every shard's part is checked before any shard is changed
+static int node_hold(nnn_node *n, bool hold, const int *streams, int n_list)
+{
+    std::vector<std::vector<int>> local, at;
+    if (int rc = node_split(n, streams, n_list, local, at)) return rc;
+    for (size_t k = 0; k < local.size(); k++)
+        if (int rc = nnn_batch_check_streams(n->shards[k].b, hold ? NODE_SS_HOLD : NODE_SS_RESUME, local[k].data(), (int)local[k].size(), nullptr, 0, false)) return rc;
+    for (size_t k = 0; k < local.size(); k++)
+        if (!local[k].empty())
+            if (int rc = hold ? nnn_batch_hold_streams(n->shards[k].b, local[k].data(), (int)local[k].size())
+                              : nnn_batch_resume_streams(n->shards[k].b, local[k].data(), (int)local[k].size())) return rc;
+    return 0;
+}
+extern "C" int nnn_node_hold_streams(nnn_node *n, const int *streams, int n_list) { return node_hold(n, true, streams, n_list); }
+extern "C" int nnn_node_resume_streams(nnn_node *n, const int *streams, int n_list) { return node_hold(n, false, streams, n_list); }
+extern "C" int nnn_node_num_held(const nnn_node *n)
+{
+    int total = 0;
+    if (n)
+        for (const auto &s : n->shards) total += nnn_batch_num_held(s.b);
+    return total;
 }

@@ -99,6 +99,19 @@ class NodeDenoiser:
         a, p = _ffi.stream_list(idx)
         self._lib.check(self._lib.L.nnn_node_reset_streams(self._h, p, a.size))
 
+    def hold_streams(self, idx):
+        """Node-global streams sit out the processing calls from the next one on (BatchDenoiser.hold_streams)."""
+        a, p = _ffi.stream_list(idx)
+        self._lib.check(self._lib.L.nnn_node_hold_streams(self._h, p, a.size))
+
+    def resume_streams(self, idx):
+        """Held streams take part again, as if the calls in between had not happened for them (BatchDenoiser.resume_streams)."""
+        a, p = _ffi.stream_list(idx)
+        self._lib.check(self._lib.L.nnn_node_resume_streams(self._h, p, a.size))
+
+    def num_held(self):
+        return int(self._lib.L.nnn_node_num_held(self._h))
+
     def export_streams(self, idx):
         """Portable records of node-global streams, uint8 [len(idx), STREAM_STATE_BYTES] (BatchDenoiser.export_streams)."""
         a, p = _ffi.stream_list(idx)
