@@ -4,19 +4,22 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libnnnoiseless_mi355x.so")
 WEIGHTS = os.path.join(HERE, "data", "weights.rnn")
 SOURCES = ["nnn_batch.hip", "nnn_resample.hip", "nnn_model.cpp", "rnnoise_capi.cpp", "nnn_node.cpp"]
 HP_SOURCE = "nnn_hp.hip"
-DEPS = SOURCES + [HP_SOURCE, "nnn_kernels.hip", "nnn_back.hip", "nnn_layout.h", "nnn_model.h", "nnn_mfma.h"]
 
 
 def _stale():
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, d) for d in DEPS] + [WEIGHTS, os.path.abspath(__file__)]
+    # every source and header of csrc/ and every public header of include/, whatever includes it: a list kept by hand goes stale with
+    # the next file
+    deps = [os.path.join(d, f) for d in (CSRC, INCLUDE) for f in os.listdir(d) if f.endswith((".hip", ".h", ".hpp", ".cpp"))]
+    deps += [WEIGHTS, os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Instruction counts of one kernel by basic block and source-line range, from device assembly built with -g (.loc directives):
 which loop of the source a run of instructions belongs to, and how many vector / LDS / scalar instructions it holds -- multiply by the
-loop's trip count (known from the source) for the dynamic count.  usage: isa_by_line.py kg.s kernel_symbol_substring [src_file_substring]"""
+loop's trip count (known from the source) for the dynamic count.  usage: isa_by_line.py kg.s kernel_symbol_substring [src_file_substring]
+(src_file_substring defaults to nnn_kernels.hip; the pitch stage -- k_pitch and its helpers -- is nnn_pitch.hip: pass that for k_pitch)"""
 import collections
 import re
 import sys

@@ -16,8 +16,9 @@ OUT = os.path.join(HERE, "_build", "libnnn_hostsim.so")
 def build(force=False):
     srcs = [os.path.join(CSRC, s) for s in ("nnn_batch.hip", "nnn_resample.hip", "nnn_model.cpp", "rnnoise_capi.cpp", "nnn_node.cpp")]
     srcs.append(os.path.join(HERE, "hostsim.cpp"))
-    deps = srcs + [os.path.join(CSRC, d) for d in ("nnn_kernels.hip", "nnn_back.hip", "nnn_layout.h", "nnn_model.h")] + [os.path.abspath(__file__)]
-    deps += [os.path.join(HERE, "hip", "hip_runtime.h"), os.path.join(HERE, "nnn_mfma.h"), os.path.join(HERE, "hostsim.cpp")]
+    # every source and header of csrc/ and include/, whatever includes it (the product's build checks the same set), and the interpreter's own
+    deps = [os.path.join(d, f) for d in (CSRC, os.path.join(ROOT, "include")) for f in os.listdir(d) if f.endswith((".hip", ".h", ".hpp", ".cpp"))]
+    deps += [os.path.join(HERE, "hip", "hip_runtime.h"), os.path.join(HERE, "nnn_mfma.h"), os.path.join(HERE, "hostsim.cpp"), os.path.abspath(__file__)]
     if not force and os.path.exists(OUT) and all(os.path.getmtime(d) <= os.path.getmtime(OUT) for d in deps):
         return OUT
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
