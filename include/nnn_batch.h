@@ -233,6 +233,20 @@ int nnn_batch_synchronize(nnn_batch *b);
 int nnn_batch_fault(const nnn_batch *b);
 /* Test hook for the above: withhold the hand-off flag of the frame `frames_ahead` frames from now (negative: off). */
 int nnn_batch_debug_withhold_flag(nnn_batch *b, int frames_ahead);
+/* Test hook: how a call of n_frames on the batch's own stream would be enqueued as the batch stands now -- its kernel launches in
+ * order, the stream of each, the events it waits for and records.  Plans only: launches nothing, changes nothing.  Writes
+ * 8 + 17 * nodes integers (an error if `cap` is smaller):
+ *   out[0] nodes, [1] frame groups, [2] 1 = spread over the internal streams, [3] schedule (0 seq, 1 lanes, 2 stages), [4] lanes,
+ *   [5] where the parameter table is filled: 0 = no launch of its own (the first high-pass launch does it; none in a call with every
+ *       stream held), 1 = the caller's stream ahead of everything, 2 = internal stream 0,
+ *   [6] 1 = that fill waits for the end of the call two calls back (the table's previous user),
+ *   [7] the group whose synthesis event the caller's stream waits for at the end of the call, -1 = none (it ran on that stream);
+ *   then per node, in enqueue order: stage (0 hp, 1 pitch, 2 fft_xp, 3 rnn, 4 synth), group, frames of the group, its first frame
+ *   within the call, stream (-1 = the caller's, 0..4 = internal), 1 = the stream's first use in the call (it waits for everything
+ *   enqueued on the caller's stream before the call), 1 = records its event, number of waits, 3 x (origin, stage, group) -- origin
+ *   0 = this call, 1 = the previous call, 2 = the end of the call two calls back (no stage or group); unused entries are -1.
+ * A node's event is slot (stage, group mod 16) of a ring the call owns; the previous call has a ring of its own. */
+int nnn_batch_debug_schedule(nnn_batch *b, int n_frames, int32_t *out, size_t cap);
 
 /* Parity taps: intermediate quantities of the most recent frame, copied to the host as
  * [n_streams][len] (float32 or int32, see nnn_tap_info).  Test/diagnostic interface.  Everything inside the pitch kernel

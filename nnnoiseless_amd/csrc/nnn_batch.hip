@@ -234,7 +234,6 @@ struct nnn_batch {
     int sp_tab_cap = 0;
     hipStream_t stream = nullptr;   // default launch stream
     hipStream_t pool[NSTREAMS] = {};   // internal streams of pipelined calls
-    uint64_t pool_call[NSTREAMS] = {}; // call in which each last waited for the caller's stream
     hipEvent_t ev[2][ST_COUNT][EVR] = {}; // [call parity]: stage s of group (k mod EVR) of that call done
     hipEvent_t ev_done[2] = {};     // [call parity]: that call complete, on the stream it was made on
     bool have_done[2] = {false, false};
@@ -1173,23 +1172,23 @@ static int ss_prepare(nnn_batch *h)
     h->ss_dims = d;
     return 0;
 }
-// The stream of a state call, ordered after everything the batch has enqueued (as process_frames orders its calls); ss_end makes it
-// the batch's most recent call.  A pipelined call before it leaves prev_pipe set: cleared, so that the next call's high-pass does not
-// start early (nnn_batch_set_inputs_ready) on rings this call writes -- what nnn_batch_load_state does.
-static hipStream_t ss_begin(nnn_batch *h, void *hip_stream, bool &ok)
+// Calls of a batch are ordered even when consecutive ones arrive on different streams (processing, state and hold calls alike):
+// call_begin picks the call's stream and, if the batch's last call was made on another one, has it wait for that call's end (`e`: how
+// that went); call_end makes this call the batch's last one.  A state or hold call also clears prev_pipe, which a pipelined call before
+// it leaves set: the next call's high-pass must not start early (nnn_batch_set_inputs_ready) on rings this call writes -- what
+// nnn_batch_load_state does.
+static hipStream_t call_begin(nnn_batch *h, void *hip_stream, hipError_t &e)
 {
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    ok = !(h->have_last && h->last_stream != st) || hipStreamWaitEvent(st, h->ev_last, 0) == hipSuccess;
+    e = (h->have_last && h->last_stream != st) ? hipStreamWaitEvent(st, h->ev_last, 0) : hipSuccess;
     return st;
 }
-static int ss_end(nnn_batch *h, hipStream_t st)
+static hipError_t call_end(nnn_batch *h, hipStream_t st)
 {
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev_last, st));
+    const hipError_t e = hipEventRecord(h->ev_last, st);
     h->last_stream = st;
     h->have_last = true;
-    h->prev_pipe = false;
-    return 0;
+    return e;
 }
 static int ss_args(nnn_batch *h, const int *streams, int n, hipStream_t st, SsArgs &a, bool &tiles)
 {
@@ -1263,9 +1262,9 @@ static int ss_call(nnn_batch *h, SsOp op, const int *streams, int n, const void 
     if (int rc = ss_prepare(h)) return rc;
     const size_t bytes = (size_t)n * NNN_STREAM_STATE_BYTES;
     if ((host_src || host_dst) && ss_stage(h, bytes)) return 1;
-    bool ok = true;
-    hipStream_t st = ss_begin(h, hip_stream, ok);
-    if (!ok) return fail("could not order the call after the batch's earlier work: %s", hipGetErrorString(hipGetLastError()));
+    hipError_t e;
+    hipStream_t st = call_begin(h, hip_stream, e);
+    if (e != hipSuccess) return fail("could not order the call after the batch's earlier work: %s", hipGetErrorString(hipGetLastError()));
     SsArgs a;
     bool tiles = false;
     if (int rc = ss_args(h, streams, n, st, a, tiles)) return rc;
@@ -1286,7 +1285,9 @@ static int ss_call(nnn_batch *h, SsOp op, const int *streams, int n, const void 
         hipLaunchKernelGGL(k_ss_parked, dim3((unsigned)n), dim3(256), 0, st, a, (const unsigned long long *)h->live, h->park, op == SS_EXPORT ? 1 : 0,
                            (unsigned *)(host_dst ? (void *)h->ss_stage : d_dst), (const unsigned *)(op == SS_IMPORT ? d_src : nullptr));
     if (host_dst) HIPCHK(hipMemcpyAsync(host_dst, h->ss_stage, bytes, hipMemcpyDeviceToHost, st));
-    if (int rc = ss_end(h, st)) return rc;
+    HIPCHK(hipGetLastError());
+    HIPCHK(call_end(h, st));
+    h->prev_pipe = false;
     if (host_src || host_dst) HIPCHK(hipStreamSynchronize(st));
     return 0;
 }
@@ -1356,9 +1357,9 @@ static int hold_call(nnn_batch *h, bool hold, const int *streams, int n)
     if (int rc = ss_prepare(h)) return rc;
     if (int rc = hold_prepare(h)) return rc;
     if (n == 0) return 0;
-    bool ok = true;
-    hipStream_t st = ss_begin(h, nullptr, ok);
-    if (!ok) return fail("could not order the call after the batch's earlier work: %s", hipGetErrorString(hipGetLastError()));
+    hipError_t e;
+    hipStream_t st = call_begin(h, nullptr, e);
+    if (e != hipSuccess) return fail("could not order the call after the batch's earlier work: %s", hipGetErrorString(hipGetLastError()));
     SsArgs a;
     bool tiles = false;
     if (int rc = ss_args(h, streams, n, st, a, tiles)) return rc;
@@ -1370,7 +1371,10 @@ static int hold_call(nnn_batch *h, bool hold, const int *streams, int n)
     // (the launch is enqueued and will flip the device's bits: the host's copy follows it whatever the bookkeeping below reports)
     for (int i = 0; i < n; i++) h->held[(size_t)streams[i]] = hold ? 1 : 0;
     h->n_held += hold ? n : -n;
-    return ss_end(h, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(call_end(h, st));
+    h->prev_pipe = false;
+    return 0;
 }
 extern "C" int nnn_batch_hold_streams(nnn_batch *h, const int *streams, int n) { return hold_call(h, true, streams, n); }
 extern "C" int nnn_batch_resume_streams(nnn_batch *h, const int *streams, int n) { return hold_call(h, false, streams, n); }
@@ -1626,8 +1630,29 @@ static CallPlan plan_call(const nnn_batch *h, int n_frames, hipStream_t st)
     return c;
 }
 
-// Common body of the process entry points: strides in BYTES, `drop` leading frames of the call produce no audio.
-//
+// A call's launches in the order they are enqueued, with the stream each goes on and the events it waits for and records
+// (plan_schedule, which reads the batch only; process_frames enqueues it, nnn_batch_debug_schedule shows it to the tests)
+constexpr int MAX_WAITS = 1 + 1 + 1;   // the most a node has, pitch: the high-pass of its group, the pitch of the group before, the scratch-set block's previous user
+static_assert(MAX_WAITS >= 1 + 1, "hp: the pitch kernel before it (hp_after) and the ring edge; rnn, synth: previous stage and previous group; fft_xp: previous stage");
+enum WaitOrigin { W_THIS = 0, W_PREV = 1, W_DONE = 2 };   // ev[this call's parity], ev[prev_par], ev_done[this call's parity] (= of the call two back)
+enum FillWhere { FILL_FOLDED = 0, FILL_CALLER = 1, FILL_POOL0 = 2 };   // k_fill_params: no launch (k_hp does it, or an idle call), caller's stream, pool[0]
+struct Wait { int origin, stage, group; };   // the event's slot is group % EVR (W_DONE: no stage or group)
+struct Node {
+    int stage, group, frames, first;   // frames of the group, its first frame within the call
+    int stream;                        // index into nnn_batch::pool, -1 = the caller's stream
+    bool first_use;                    // the stream's first launch of the call: waits for ev_in (everything before the call)
+    bool record;                       // records ev[parity][stage][group % EVR]: it has a consumer on another stream
+    bool fill;                         // the launch that fills the parameter table on its way (FILL_FOLDED)
+    int n_waits;
+    Wait waits[MAX_WAITS];
+};
+struct Schedule {
+    std::vector<Node> nodes;
+    int fill = FILL_FOLDED;
+    bool fill_after_done = false;      // FILL_POOL0: behind ev_done[parity], the table's previous user
+    int last_syn = -1;                 // the group whose synthesis event the caller's stream waits for at the end (-1: it ran there)
+};
+
 // A call is cut into groups of up to GROUP frames; group k uses scratch-set block (group_count mod depth).  Short calls
 // (and profiling) run the groups' stages back to back on the caller's stream.  Longer calls spread over the batch's
 // internal streams so that independent stages overlap (at 4096 streams a lone stage cannot fill the GPU):
@@ -1639,6 +1664,85 @@ static CallPlan plan_call(const nnn_batch *h, int n_frames, hipStream_t st)
 // block's previous user (synth of group k - depth, before pitch of group k); the history rings (synth of the group holding the
 // newest frame whose history slots group k's high-pass overwrites).  Everything before this call is ordered by the caller's
 // stream, which every internal stream waits for at its first use and which waits for the last synth at the end.
+// The schedule of the batch's NEXT call (parity of call_count + 1), cut and set as `cp` says.
+static Schedule plan_schedule(const nnn_batch *h, const CallPlan &cp)
+{
+    Schedule sc;
+    const int n_groups = (int)cp.sizes.size(), par = (int)((h->call_count + 1) & 1);
+    sc.fill = cp.early_hp ? FILL_POOL0 : (cp.fold_fill ? FILL_FOLDED : FILL_CALLER);
+    sc.fill_after_done = cp.early_hp && h->have_done[par];   // the table's previous user (two calls back)
+    if (cp.idle) return sc;
+    // index into h->pool; -1 = the caller's stream (lane 0 of the lanes schedule, the synthesis chain of the stages one, every launch of a
+    // call that is not pipelined)
+    auto stream_of = [&](int s, int k) -> int {
+        if (!cp.pipe) return -1;
+        if (cp.sched == SCHED_STAGES) return s == ST_HP ? 0 : (s == ST_PITCH ? 1 : (s == ST_FFT ? 2 : (s == ST_RNN ? 3 : -1)));
+        return s == ST_HP ? 0 : (k % cp.lanes) - (k % cp.lanes == 0 ? 1 : 0);
+    };
+    // which (stage, group) nodes have a consumer on another stream: only those record an event
+    auto consumers_elsewhere = [&](int s, int k) {
+        const int me = stream_of(s, k);
+        if (s + 1 < ST_COUNT && stream_of(s + 1, k) != me) return true;
+        if ((s == ST_HP || s == ST_PITCH || s == ST_RNN || s == ST_SYN) && k + 1 < n_groups && stream_of(s, k + 1) != me) return true;
+        if (s == ST_SYN) return true;   // scratch-set / ring edges and the end of the call
+        if (cp.hp_after && s == ST_PITCH) return true;
+        return false;
+    };
+    bool used[NSTREAMS] = {cp.early_hp};   // (pool[0] of an early_hp call starts with the table's fill: no wait for the caller's stream on that one)
+    const int pn = (int)h->prev_first.size();   // groups of the previous call
+    sc.nodes.reserve((size_t)n_groups * ST_COUNT);
+    for (int k = 0, t = 0; k < n_groups; t += cp.sizes[k++]) {
+        const int g = cp.sizes[k];
+        for (int s = 0; s < ST_COUNT; s++) {
+            Node n = {};
+            const int si = stream_of(s, k);
+            n.stage = s, n.group = k, n.frames = g, n.first = t, n.stream = si;
+            n.first_use = si >= 0 && !used[si];   // everything before the call comes first
+            if (si >= 0) used[si] = true;
+            n.fill = cp.fold_fill && k == 0 && s == ST_HP;
+            n.record = cp.pipe && consumers_elsewhere(s, k);
+            auto wait = [&](int origin, int ds, int dk) { n.waits[n.n_waits++] = Wait{origin, ds, dk}; };
+            auto wait_for = [&](int ds, int dk) {
+                if (dk < 0 || dk < k - EVR + 1) return;   // before this call (ordered by ev_in) or long retired
+                if (stream_of(ds, dk) != si) wait(W_THIS, ds, dk);
+            };
+            if (s > 0) wait_for(s - 1, k);
+            if (s == ST_HP || s == ST_PITCH || s == ST_RNN || s == ST_SYN) wait_for(s, k - 1);
+            if (s == ST_PITCH) wait_for(ST_SYN, k - h->depth);
+            if (s == ST_HP && cp.hp_after) {   // behind the previous group's pitch kernel (the previous call's last one for the first group)
+                if (k > 0) wait_for(ST_PITCH, k - 1);
+                else if (cp.early_hp && pn > 0) wait(W_PREV, ST_PITCH, pn - 1);
+            }
+            if (s == ST_HP && cp.pipe) {
+                // slots written now held frames (newest of this group) - nslot and older; their last readers are the
+                // frames up to 3 later
+                const int need = t + g - 1 + 3 - h->nslot;
+                int dk = -1;   // the group of this call that holds frame `need` (none: it precedes the call)
+                for (int j = 0; j < k; j++)
+                    if (sc.nodes[(size_t)j * ST_COUNT].first <= need) dk = j;
+                wait_for(ST_SYN, dk);
+                if (cp.early_hp && need < 0) {
+                    // the frame lies in the previous call: the synthesis of its group there; older still: the call before that
+                    const long long pf = (long long)h->frame_count + need - (long long)h->prev_frame0;
+                    int pj = -1;
+                    for (int j = 0; j < pn; j++)
+                        if (h->prev_first[j] <= pf) pj = j;
+                    if (pf >= 0 && pj >= 0 && pn - pj < EVR) wait(W_PREV, ST_SYN, pj);
+                    else if (h->have_done[par]) wait(W_DONE, 0, 0);   // (this parity's last call = the one before the previous one)
+                }
+            }
+            sc.nodes.push_back(n);
+        }
+    }
+    if (stream_of(ST_SYN, n_groups - 1) >= 0) sc.last_syn = n_groups - 1;
+    return sc;
+}
+static hipEvent_t wait_event(const nnn_batch *h, int par, const Wait &w)
+{
+    return w.origin == W_DONE ? h->ev_done[par] : h->ev[w.origin == W_PREV ? h->prev_par : par][w.stage][w.group % EVR];
+}
+
+// Common body of the process entry points: strides in BYTES, `drop` leading frames of the call produce no audio.
 static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_vad, int n_frames, int fmt, int channels,
                           long long group_stride, long long frame_stride, int drop, void *hip_stream)
 {
@@ -1659,9 +1763,9 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
                                 "(export GPU_MAX_HW_QUEUES=8 before the process starts -- INTEGRATION.md; any value of the variable silences this note)\n", h->device);
         }
     }
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    // calls are ordered even when consecutive ones arrive on different streams
-    if (h->have_last && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_last, 0));
+    hipError_t e;
+    hipStream_t st = call_begin(h, hip_stream, e);
+    if (e != hipSuccess) return fail("hipStreamWaitEvent(st, h->ev_last, 0) failed: %s", hipGetErrorString(e));
     StepParams v0;
     v0.in = (const char *)d_in;
     v0.out = (char *)d_out;
@@ -1691,109 +1795,49 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
         h->prev_pipe = false;
     }
     const CallPlan cp = plan_call(h, n_frames, st);
+    const Schedule sc = plan_schedule(h, cp);
     const int n_groups = (int)cp.sizes.size();
     h->call_count += 1;
     const int par = (int)(h->call_count & 1);
     StepParams *const tab = h->sp_tab + (size_t)par * h->sp_tab_cap;   // this call's parameter table
     const uint64_t frame0 = h->frame_count;
     bool ok = true;
-    auto chk = [&](hipError_t e) { ok = ok && e == hipSuccess; };
-    if (cp.early_hp) {
-        if (h->have_done[par]) chk(hipStreamWaitEvent(h->pool[0], h->ev_done[par], 0));   // the table's previous user (two calls back)
-        hipLaunchKernelGGL(k_fill_params, dim3((n_frames + 63) / 64), dim3(64), 0, h->pool[0], tab, v0, n_frames, h->nslot);
-        h->pool_call[0] = h->call_count;   // (no wait for the caller's stream on this one)
-    } else if (!cp.fold_fill) {
-        hipLaunchKernelGGL(k_fill_params, dim3((n_frames + 63) / 64), dim3(64), 0, st, tab, v0, n_frames, h->nslot);
+    if (sc.fill != FILL_FOLDED) {
+        hipStream_t fs = sc.fill == FILL_POOL0 ? h->pool[0] : st;
+        if (sc.fill_after_done) ok &= hipStreamWaitEvent(fs, h->ev_done[par], 0) == hipSuccess;
+        hipLaunchKernelGGL(k_fill_params, dim3((n_frames + 63) / 64), dim3(64), 0, fs, tab, v0, n_frames, h->nslot);
     }
-    if (!cp.pipe) {
-        for (int k = 0, t = 0; k < n_groups; k++) {
-            const int g = cp.sizes[k], set0 = (int)(h->group_count % h->depth) * h->gmax;
-            plan_group(h, g, h->plan);
-            for (int s = 0; s < ST_COUNT && !cp.idle; s++) launch_stage(h, s, set0, h->plan, tab + t, st, h->profiling, plain_out, (cp.fold_fill && k == 0) ? &v0 : nullptr, n_frames);
-            h->group_count += 1;
-            h->frame_count += g;
-            h->last_set = set0 + g - 1;
-            t += g;
+    if (cp.pipe) ok &= hipEventRecord(h->ev_in, st) == hipSuccess;
+    size_t i = 0;
+    for (int k = 0; k < n_groups; k++) {   // (an idle call has groups and no nodes)
+        const int g = cp.sizes[k], set0 = (int)(h->group_count % h->depth) * h->gmax;
+        plan_group(h, g, h->plan);
+        for (; i < sc.nodes.size() && sc.nodes[i].group == k; i++) {
+            const Node &n = sc.nodes[i];
+            if (n.stream >= 0 && !h->pool[n.stream]) ok &= hipStreamCreateWithFlags(&h->pool[n.stream], hipStreamNonBlocking) == hipSuccess;
+            hipStream_t ss = n.stream < 0 ? st : h->pool[n.stream];
+            if (n.first_use) ok &= hipStreamWaitEvent(ss, h->ev_in, 0) == hipSuccess;
+            for (int w = 0; w < n.n_waits; w++) ok &= hipStreamWaitEvent(ss, wait_event(h, par, n.waits[w]), 0) == hipSuccess;
+            launch_stage(h, n.stage, set0, h->plan, tab + n.first, ss, h->profiling, plain_out, n.fill ? &v0 : nullptr, n_frames);
+            if (n.record) ok &= hipEventRecord(h->ev[par][n.stage][k % EVR], ss) == hipSuccess;
         }
-        h->prev_pipe = false;
-    } else {
-        chk(hipEventRecord(h->ev_in, st));
-        // index into h->pool; -1 = the caller's stream (lane 0 of the lanes schedule, the synthesis chain of the stages one)
-        auto stream_of = [&](int s, int k) -> int {
-            if (cp.sched == SCHED_STAGES) return s == ST_HP ? 0 : (s == ST_PITCH ? 1 : (s == ST_FFT ? 2 : (s == ST_RNN ? 3 : -1)));
-            return s == ST_HP ? 0 : (k % cp.lanes) - (k % cp.lanes == 0 ? 1 : 0);
-        };
-        std::vector<int> first(n_groups);   // first frame (within the call) of every group
-        for (int k = 0, t = 0; k < n_groups; k++) { first[k] = t; t += cp.sizes[k]; }
-        // which (stage, group) nodes have a consumer on another stream: only those record an event
-        auto consumers_elsewhere = [&](int s, int k) {
-            const int me = stream_of(s, k);
-            if (s + 1 < ST_COUNT && stream_of(s + 1, k) != me) return true;
-            if ((s == ST_HP || s == ST_PITCH || s == ST_RNN || s == ST_SYN) && k + 1 < n_groups && stream_of(s, k + 1) != me) return true;
-            if (s == ST_SYN) return true;   // scratch-set / ring edges and the end of the call
-            if (cp.hp_after && s == ST_PITCH) return true;
-            return false;
-        };
-        for (int k = 0; k < n_groups; k++) {
-            const int g = cp.sizes[k], set0 = (int)(h->group_count % h->depth) * h->gmax;
-            plan_group(h, g, h->plan);
-            for (int s = 0; s < ST_COUNT; s++) {
-                const int si = stream_of(s, k);
-                if (si >= 0 && !h->pool[si]) chk(hipStreamCreateWithFlags(&h->pool[si], hipStreamNonBlocking));
-                hipStream_t ss = si < 0 ? st : h->pool[si];
-                if (si >= 0 && h->pool_call[si] != h->call_count) {   // first use in this call: everything before the call comes first
-                    chk(hipStreamWaitEvent(ss, h->ev_in, 0));
-                    h->pool_call[si] = h->call_count;
-                }
-                auto wait_for = [&](int ds, int dk) {
-                    if (dk < 0 || dk < k - EVR + 1) return;   // before this call (ordered by ev_in) or long retired
-                    if (stream_of(ds, dk) != si) chk(hipStreamWaitEvent(ss, h->ev[par][ds][dk % EVR], 0));
-                };
-                if (s > 0) wait_for(s - 1, k);
-                if (s == ST_HP || s == ST_PITCH || s == ST_RNN || s == ST_SYN) wait_for(s, k - 1);
-                if (s == ST_PITCH) wait_for(ST_SYN, k - h->depth);
-                if (s == ST_HP && cp.hp_after) {   // behind the previous group's pitch kernel (the previous call's last one for the first group)
-                    const int pn = (int)h->prev_first.size();
-                    if (k > 0) wait_for(ST_PITCH, k - 1);
-                    else if (cp.early_hp && pn > 0) chk(hipStreamWaitEvent(ss, h->ev[h->prev_par][ST_PITCH][(pn - 1) % EVR], 0));
-                }
-                if (s == ST_HP) {
-                    // slots written now held frames (newest of this group) - nslot and older; their last readers are the
-                    // frames up to 3 later
-                    const int need = first[k] + g - 1 + 3 - h->nslot;
-                    int dk = -1;   // the group of this call that holds frame `need` (none: it precedes the call)
-                    for (int j = 0; j < k; j++)
-                        if (first[j] <= need) dk = j;
-                    wait_for(ST_SYN, dk);
-                    if (cp.early_hp && need < 0) {
-                        // the frame lies in the previous call: the synthesis of its group there; older still: the call before that
-                        const long long pn = (long long)frame0 + need - (long long)h->prev_frame0;
-                        int pj = -1;
-                        for (int j = 0; j < (int)h->prev_first.size(); j++)
-                            if (h->prev_first[j] <= pn) pj = j;
-                        if (pn >= 0 && pj >= 0 && (int)h->prev_first.size() - pj < EVR) chk(hipStreamWaitEvent(ss, h->ev[h->prev_par][ST_SYN][pj % EVR], 0));
-                        else if (h->have_done[par]) chk(hipStreamWaitEvent(ss, h->ev_done[par], 0));   // (par = the call before the previous one)
-                    }
-                }
-                launch_stage(h, s, set0, h->plan, tab + first[k], ss, false, plain_out);
-                if (consumers_elsewhere(s, k)) chk(hipEventRecord(h->ev[par][s][k % EVR], ss));
-            }
-            h->group_count += 1;
-            h->frame_count += g;
-            h->last_set = set0 + g - 1;
-        }
-        if (stream_of(ST_SYN, n_groups - 1) >= 0) chk(hipStreamWaitEvent(st, h->ev[par][ST_SYN][(n_groups - 1) % EVR], 0));
-        h->prev_pipe = true;
+        h->group_count += 1;
+        h->frame_count += g;
+        h->last_set = set0 + g - 1;
+    }
+    if (sc.last_syn >= 0) ok &= hipStreamWaitEvent(st, h->ev[par][ST_SYN][sc.last_syn % EVR], 0) == hipSuccess;
+    // a pipelined call: the next call's high-pass chain may be started before it has drained (plan_call's early_hp)
+    h->prev_pipe = cp.pipe;
+    if (cp.pipe) {
         h->prev_st = st;
         h->prev_frame0 = frame0;
         h->prev_par = par;
-        h->prev_first = first;
+        h->prev_first.clear();
+        for (int k = 0; k < n_groups; k++) h->prev_first.push_back(sc.nodes[(size_t)k * ST_COUNT].first);
     }
-    chk(hipEventRecord(h->ev_done[par], st));
+    ok &= hipEventRecord(h->ev_done[par], st) == hipSuccess;
     h->have_done[par] = true;
-    chk(hipEventRecord(h->ev_last, st));
-    h->last_stream = st;
-    h->have_last = true;
+    ok &= call_end(h, st) == hipSuccess;
     if (!ok) return fail("stream/event call failed while enqueueing frames: %s", hipGetErrorString(hipGetLastError()));
     HIPCHK(hipGetLastError());
     if (h->profiling) {
@@ -2248,6 +2292,30 @@ extern "C" int nnn_batch_debug_withhold_flag(nnn_batch *h, int frames_ahead)
     for (int set = 0; set < h->nset; set++) {
         h->b[set].dbg_withhold = seq;
         h->b[set].handoff_ticks = seq ? 20000000ll : HANDOFF_TICKS;   // the withheld flag is given up on after 0.2 s
+    }
+    return 0;
+}
+// Test hook: the schedule a call of n_frames on the batch's own stream would get now, as integers (include/nnn_batch.h).  Plans only.
+extern "C" int nnn_batch_debug_schedule(nnn_batch *h, int n_frames, int32_t *out, size_t cap)
+{
+    if (!h || !out) return fail("null argument");
+    if (n_frames < 1) return fail("n_frames must be at least 1");
+    CallPlan cp = plan_call(h, n_frames, h->stream);
+    if (n_frames > h->sp_tab_cap) cp.early_hp = false;   // (the call would first grow its parameter table, which drains the batch: prev_pipe off)
+    const Schedule sc = plan_schedule(h, cp);
+    constexpr size_t HEAD = 8, PER_NODE = 8 + 3 * MAX_WAITS;
+    if (cap < HEAD + PER_NODE * sc.nodes.size()) return fail("schedule buffer too small: %zu entries needed", HEAD + PER_NODE * sc.nodes.size());
+    const int32_t head[HEAD] = {(int32_t)sc.nodes.size(), (int32_t)cp.sizes.size(), cp.pipe, cp.sched, cp.lanes, sc.fill, sc.fill_after_done, sc.last_syn};
+    memcpy(out, head, sizeof(head));
+    out += HEAD;
+    for (const Node &n : sc.nodes) {
+        const int32_t v[8] = {n.stage, n.group, n.frames, n.first, n.stream, n.first_use, n.record, n.n_waits};
+        memcpy(out, v, sizeof(v));
+        for (int w = 0; w < MAX_WAITS; w++) {
+            const Wait x = w < n.n_waits ? n.waits[w] : Wait{-1, -1, -1};
+            out[8 + 3 * w] = x.origin, out[9 + 3 * w] = x.stage, out[10 + 3 * w] = x.group;
+        }
+        out += PER_NODE;
     }
     return 0;
 }

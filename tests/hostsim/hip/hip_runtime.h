@@ -125,8 +125,11 @@ static inline hipError_t hipSetDevice(int) { return hipSuccess; }
 static inline hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
 static inline hipError_t hipGetDeviceCount(int *n) { *n = 2; return hipSuccess; }   // (two ordinals, one interpreter: what the node tests need)
 static inline hipError_t hipDeviceGetPCIBusId(char *, int, int) { return 1; }   // (the interpreter's "device" has no PCI function)
-static inline hipError_t hipStreamCreate(hipStream_t *s) { *s = nullptr; return hipSuccess; }
-static inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = nullptr; return hipSuccess; }
+// (streams do nothing here -- kernels run to completion in issue order -- but each has a handle of its own, never null, as the real
+// runtime's have: the host code tells "not created yet" and "the same stream as last time" by them)
+inline hipStream_t hostsim_new_stream() { static uintptr_t n = 0; return (hipStream_t)++n; }
+static inline hipError_t hipStreamCreate(hipStream_t *s) { *s = hostsim_new_stream(); return hipSuccess; }
+static inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = hostsim_new_stream(); return hipSuccess; }
 static inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
 enum { hipStreamNonBlocking = 1 };
 hipError_t hipEventCreate(hipEvent_t *e);

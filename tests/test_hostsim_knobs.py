@@ -6,6 +6,7 @@ import pytest
 
 @pytest.mark.parametrize("env", [{"NNN_SCHED": "seq"}, {"NNN_SCHED": "lanes", "NNN_LANES": "2"}, {"NNN_SCHED": "stages"}, {"NNN_LANES": "3"}])
 def test_schedule_knobs_give_the_same_bits(hostsim_lib, monkeypatch, env):
+    """(The interpreter runs kernels in issue order whatever stream they are on: a missing event edge does not show here -- test_hostsim_schedule.py.)"""
     import nnnoiseless_amd as nn
     from nnnoiseless_amd.synthetic import make_streams
     S, T = 3, 34                                   # (calls of 32 frames or more are the ones a schedule spreads over streams)
