@@ -247,6 +247,15 @@ int nnn_batch_debug_withhold_flag(nnn_batch *b, int frames_ahead);
  *   0 = this call, 1 = the previous call, 2 = the end of the call two calls back (no stage or group); unused entries are -1.
  * A node's event is slot (stage, group mod 16) of a ring the call owns; the previous call has a ring of its own. */
 int nnn_batch_debug_schedule(nnn_batch *b, int n_frames, int32_t *out, size_t cap);
+/* Test hook: the route nnn_batch_process_pcm_host would take for n_frames of `layout` as the batch stands now (has_vad: a VAD buffer is
+ * passed).  Plans only: allocates nothing, copies nothing, changes nothing.
+ *   out[0] route: 0 = zero-copy (the kernels work on mapped page-locked host memory), 1 = staged in one piece, 2 = staged in chunks over
+ *          two copy streams,
+ *   [1] frames per chunk and [2] chunks (n_frames and 1 unless the route is 2), [3] bytes of the layout's bounding span (what is
+ *   shipped), [4] bytes of the VAD rows (0 without), [5] offset of the VAD rows behind the span in a host image of both,
+ *   [6] 1 = the first frame is dropped (discard_first on a fresh batch), [7] 1 = a one-piece call would copy the VAD rows back around
+ *   held streams. */
+int nnn_batch_debug_host_plan(nnn_batch *b, int n_frames, const nnn_pcm_layout *layout, int has_vad, int64_t out[8]);
 
 /* Parity taps: intermediate quantities of the most recent frame, copied to the host as
  * [n_streams][len] (float32 or int32, see nnn_tap_info).  Test/diagnostic interface.  Everything inside the pitch kernel

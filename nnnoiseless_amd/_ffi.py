@@ -19,7 +19,7 @@ BATCH_SYMBOLS = [
     "nnn_batch_set_taps", "nnn_batch_set_schedule", "nnn_batch_set_inputs_ready", "nnn_debug_activations",
     "nnn_tap_info", "nnn_batch_read_tap", "nnn_batch_set_profiling", "nnn_batch_num_kernels",
     "nnn_batch_kernel_name", "nnn_batch_read_kernel_times", "nnn_batch_set_graph", "nnn_batch_set_pipeline", "nnn_batch_read_stamps",
-    "nnn_host_alloc", "nnn_host_free", "nnn_last_error", "nnn_batch_fault", "nnn_batch_debug_withhold_flag", "nnn_batch_debug_schedule", "nnn_batch_set_frame_log",
+    "nnn_host_alloc", "nnn_host_free", "nnn_last_error", "nnn_batch_fault", "nnn_batch_debug_withhold_flag", "nnn_batch_debug_schedule", "nnn_batch_debug_host_plan", "nnn_batch_set_frame_log",
     "nnn_batch_create_opts", "nnn_batch_max_group_frames", "nnn_batch_device_bytes", "nnn_batch_set_back_end", "nnn_device_local_cpulist",
     "nnn_batch_reset_streams", "nnn_batch_export_streams", "nnn_batch_import_streams", "nnn_batch_export_streams_device",
     "nnn_batch_import_streams_device", "nnn_batch_hold_streams", "nnn_batch_resume_streams", "nnn_batch_num_held", "nnn_batch_held_mask",
@@ -136,6 +136,7 @@ class Library:
         L.nnn_batch_set_inputs_ready.argtypes = [vp, i32]
         for name, at in (("nnn_batch_set_frame_log", [vp, vp, sz]), ("nnn_batch_fault", [vp]), ("nnn_batch_debug_withhold_flag", [vp, i32]),
                          ("nnn_batch_debug_schedule", [vp, i32, C.POINTER(C.c_int32), sz]),
+                         ("nnn_batch_debug_host_plan", [vp, i32, C.POINTER(PcmLayout), i32, C.POINTER(C.c_int64)]),
                          ("nnn_batch_create_opts", [C.POINTER(vp), C.POINTER(i32), i32, i32, C.POINTER(BatchOpts)]),
                          ("nnn_batch_max_group_frames", [vp]), ("nnn_batch_device_bytes", [vp]), ("nnn_batch_set_back_end", [vp, i32])):
             if hasattr(L, name):   # (experimental builds of older sources, loaded through NNN_LIBRARY, lack the newest entry points)

@@ -111,7 +111,7 @@ constexpr long long HANDOFF_TICKS = 10000ll * 100000ll;   // Buffers::handoff_ti
 
 // Every setting that picks a kernel or a schedule.  read_paths fills it from the environment at batch creation; the setters change
 // back_mode, use_pipeline, inputs_ready and (nnn_batch_set_schedule) sched, n_lanes and sched_auto later.  Only creation, the two plan
-// functions (plan_call, plan_group) and the host-buffer chunk rules read it.
+// functions (plan_call, plan_group) and the host-buffer plans (plan_host_call, plan_train_chunk) read it.
 struct Paths {
     int sched = SCHED_LANES;       // how a multi-frame call spreads over streams (env NNN_SCHED: seq | lanes | stages)
     bool sched_auto = true;        // nobody chose a schedule (NNN_SCHED / NNN_LANES / nnn_batch_set_schedule): the rule of plan_call
@@ -185,6 +185,37 @@ struct GroupPlan {
     uint8_t *rnn = nullptr;        // RnnKernel of each resident model group (made at creation)
 };
 
+// A runtime buffer that is kept from call to call (per-call hipMalloc / hipFree cost more than a frame) and replaced by a larger one when
+// a call needs more.  `cap` is in the site's own unit (bytes, entries, frames).
+enum MemKind : uint8_t { MEM_DEVICE, MEM_PINNED, MEM_MAPPED };   // hipMalloc; page-locked host memory; the same, mapped into the device's address space
+template <class T> struct GrowBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    MemKind kind = MEM_DEVICE;
+    int release()
+    {
+        if (p) HIPCHK(kind == MEM_DEVICE ? hipFree(p) : hipHostFree(p));
+        p = nullptr, cap = 0;
+        return 0;
+    }
+    hipError_t alloc(size_t n) { return kind == MEM_DEVICE ? hipMalloc((void **)&p, n) : hipHostMalloc((void **)&p, n, kind == MEM_MAPPED ? hipHostMallocMapped : 0); }
+};
+static int quiesce(nnn_batch *h);
+// `a` (and a companion `b` that grows with it) replaced by buffers of a_bytes (b_bytes), capacity `cap`: under the runtime lock and, where
+// `drain` says that enqueued work may still use the old ones, once everything the batch has enqueued is complete.
+template <class A, class B = char> static int grow(nnn_batch *h, bool drain, GrowBuf<A> &a, size_t a_bytes, size_t cap, GrowBuf<B> *b = nullptr, size_t b_bytes = 0)
+{
+    NNN_RT_LOCK;
+    if (int rc = drain ? quiesce(h) : 0) return rc;
+    if (int rc = a.release()) return rc;
+    if (int rc = b ? b->release() : 0) return rc;
+    HIPCHK(a.alloc(a_bytes));
+    if (b) HIPCHK(b->alloc(b_bytes));
+    a.cap = cap;   // (only now that every allocation has succeeded: a failed grow leaves the capacity zero, and the next call tries again)
+    if (b) b->cap = cap;
+    return 0;
+}
+
 struct nnn_batch {
     Buffers b[NSET];               // same state, NSET scratch sets (views into one allocation per scratch array: set s lies
                                    // s * S_pad * LEN after set 0, see frame_view); a group of frames takes consecutive sets
@@ -220,18 +251,16 @@ struct nnn_batch {
     int last_set = 0;              // scratch set of the most recent frame (parity taps)
     std::vector<void *> allocs;     // everything hipMalloc'ed
     std::vector<std::pair<void *, size_t>> state_bufs;  // zeroed by reset, copied by clone / save / load
-    char *stage = nullptr;          // device staging of the host-buffer entry points (grow-only)
-    float *stage_vad = nullptr;
-    size_t stage_cap = 0, stage_vad_cap = 0;
+    GrowBuf<char> stage;            // device staging of the host-buffer entry points (capacities in bytes)
+    GrowBuf<float> stage_vad;
     std::vector<char> stage_host;   // host side of the copy back
     // small host-buffer calls (the drop-in single-stream surface: a batch of one, a frame per call) skip both copies: the kernels read the
     // input from, and write the audio and the VAD into, page-locked host memory mapped into the device's address space (round 6)
-    char *zc_host = nullptr, *zc_dev = nullptr;
-    size_t zc_cap = 0;
+    GrowBuf<char> zc_host{nullptr, 0, MEM_MAPPED};   // (made on first use, ZC_MAX bytes)
+    char *zc_dev = nullptr;
     hipStream_t copy_in = nullptr, copy_out = nullptr;   // host-buffer calls in chunks: uploads, downloads (created on first use)
     std::vector<hipEvent_t> ev_up, ev_run;               // per chunk: uploaded, processed
-    StepParams *sp_tab = nullptr;   // device, per-frame parameter table of a call
-    int sp_tab_cap = 0;
+    GrowBuf<StepParams> sp_tab;     // device, per-frame parameter table of a call: two tables of `cap` frames, consecutive calls alternate
     hipStream_t stream = nullptr;   // default launch stream
     hipStream_t pool[NSTREAMS] = {};   // internal streams of pipelined calls
     hipEvent_t ev[2][ST_COUNT][EVR] = {}; // [call parity]: stage s of group (k mod EVR) of that call done
@@ -267,13 +296,11 @@ struct nnn_batch {
     int *ss_flag = nullptr;            // device: the record check of a device import found a bad record (the import kernel then writes nothing)
     volatile int *ss_bad_host = nullptr;   // host view of the same verdict (page-locked, mapped): reported by nnn_batch_synchronize
     int *ss_bad_dev = nullptr;
-    int *ss_idx = nullptr;             // device copy of a long scattered index list, and its page-locked source
-    int *ss_idx_pin = nullptr;
-    size_t ss_idx_cap = 0;
+    GrowBuf<int> ss_idx;               // device copy of a long scattered index list, and its page-locked source (capacity in entries)
+    GrowBuf<int> ss_idx_pin{nullptr, 0, MEM_PINNED};
     hipEvent_t ev_ss_idx = nullptr;    // the last copy out of ss_idx_pin is done
     bool ss_idx_busy = false;
-    char *ss_stage = nullptr;          // the host variants' records on the device (grow-only)
-    size_t ss_stage_cap = 0;
+    GrowBuf<char> ss_stage;            // the host variants' records on the device (capacity in bytes)
     // held streams (nnn_batch_hold_streams), made on the first hold and counted in device_bytes
     unsigned *park = nullptr;          // device: the parked record of every stream, [S][NNN_STREAM_STATE_BYTES / 4]; valid while the stream is held
     unsigned long long *live = nullptr;   // device: Buffers::live of every scratch set's argument block
@@ -367,21 +394,21 @@ extern "C" void nnn_batch_destroy(nnn_batch *h)
     for (hipEvent_t e : h->evp) hipEventDestroy(e);
     for (void *p : h->allocs) hipFree(p);
     if (h->fault_host) hipHostFree((void *)h->fault_host);
-    if (h->sp_tab) hipFree(h->sp_tab);
+    h->sp_tab.release();
     for (hipEvent_t e : h->ev_up) hipEventDestroy(e);
     for (hipEvent_t e : h->ev_run) hipEventDestroy(e);
     if (h->copy_in) hipStreamDestroy(h->copy_in);
     if (h->copy_out) hipStreamDestroy(h->copy_out);
-    if (h->stage) hipFree(h->stage);
-    if (h->stage_vad) hipFree(h->stage_vad);
-    if (h->zc_host) hipHostFree(h->zc_host);
+    h->stage.release();
+    h->stage_vad.release();
+    h->zc_host.release();
     if (h->ss_dims) hipFree(h->ss_dims);
     if (h->ss_flag) hipFree(h->ss_flag);
     if (h->ss_bad_host) hipHostFree((void *)h->ss_bad_host);
-    if (h->ss_idx) hipFree(h->ss_idx);
-    if (h->ss_idx_pin) hipHostFree(h->ss_idx_pin);
+    h->ss_idx.release();
+    h->ss_idx_pin.release();
     if (h->ev_ss_idx) hipEventDestroy(h->ev_ss_idx);
-    if (h->ss_stage) hipFree(h->ss_stage);
+    h->ss_stage.release();
     delete[] h->plan.rnn;
     for (int i = 0; i < NSTREAMS; i++)
         if (h->pool[i]) hipStreamDestroy(h->pool[i]);
@@ -427,7 +454,6 @@ static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *g
     h->device = device;
     HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-
     HIPCHK(hipEventCreateWithFlags(&h->ev_last, hipEventDisableTiming));
     // (the internal streams of pipelined calls are created on first use: HIP spreads streams over a few hardware queues in
     // creation order, and a stream that shares its queue with the caller's blocks behind the caller's waits)
@@ -536,8 +562,7 @@ static int create_impl(nnn_batch *h, const RNNModel *const *models, const int *g
     }
     HIPCHK(dalloc(h, &b.ticket, 1, false));
     b.handoff_ticks = HANDOFF_TICKS;
-    HIPCHK(hipMalloc((void **)&h->sp_tab, 2 * 64 * sizeof(StepParams)));   // two tables: consecutive calls alternate
-    h->sp_tab_cap = 64;
+    if (int rc = grow(h, false, h->sp_tab, 2 * 64 * sizeof(StepParams), 64)) return rc;
     // tables
     std::vector<float> window, dct, tansig, bin_frac;
     std::vector<float2> tw;
@@ -1205,25 +1230,16 @@ static int ss_args(nnn_batch *h, const int *streams, int n, hipStream_t st, SsAr
         for (int i = 0; i < n; i++) a.small[i] = streams[i];
     } else {
         a.mode = 2;
-        if ((size_t)n > h->ss_idx_cap) {
-            NNN_RT_LOCK;
-            if (int rc = quiesce(h)) return rc;   // (the old list may still be read)
-            if (h->ss_idx) HIPCHK(hipFree(h->ss_idx));
-            if (h->ss_idx_pin) HIPCHK(hipHostFree(h->ss_idx_pin));
-            h->ss_idx = nullptr;
-            h->ss_idx_pin = nullptr;
-            h->ss_idx_cap = 0;
+        if ((size_t)n > h->ss_idx.cap) {   // (drained first: the old list may still be read)
+            if (int rc = grow(h, true, h->ss_idx, (size_t)n * sizeof(int), (size_t)n, &h->ss_idx_pin, (size_t)n * sizeof(int))) return rc;
             h->ss_idx_busy = false;
-            HIPCHK(hipMalloc((void **)&h->ss_idx, (size_t)n * sizeof(int)));
-            HIPCHK(hipHostMalloc((void **)&h->ss_idx_pin, (size_t)n * sizeof(int), 0));
-            h->ss_idx_cap = (size_t)n;
         }
         if (h->ss_idx_busy) HIPCHK(hipEventSynchronize(h->ev_ss_idx));   // the page-locked list of the previous call has been copied
-        memcpy(h->ss_idx_pin, streams, (size_t)n * sizeof(int));
-        HIPCHK(hipMemcpyAsync(h->ss_idx, h->ss_idx_pin, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+        memcpy(h->ss_idx_pin.p, streams, (size_t)n * sizeof(int));
+        HIPCHK(hipMemcpyAsync(h->ss_idx.p, h->ss_idx_pin.p, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
         HIPCHK(hipEventRecord(h->ev_ss_idx, st));
         h->ss_idx_busy = true;
-        a.idx = h->ss_idx;
+        a.idx = h->ss_idx.p;
     }
     const int nslot = h->nslot, N = (int)(h->frame_count % (uint64_t)nslot);
     a.rb_in = ring_base((N + nslot - 1) % nslot, nslot);
@@ -1243,17 +1259,6 @@ static void ss_launch(nnn_batch *h, bool to_records, const SsArgs &a, bool tiles
         else hipLaunchKernelGGL(k_ss_import_streams, dim3(grid), dim3(256), 0, st, b, a, (const unsigned *)src);
     }
 }
-static int ss_stage(nnn_batch *h, size_t bytes)
-{
-    if (bytes <= h->ss_stage_cap) return 0;
-    NNN_RT_LOCK;
-    if (h->ss_stage) HIPCHK(hipFree(h->ss_stage));   // (host variants wait for their work: nothing reads it now)
-    h->ss_stage = nullptr;
-    h->ss_stage_cap = 0;
-    HIPCHK(hipMalloc((void **)&h->ss_stage, bytes));
-    h->ss_stage_cap = bytes;
-    return 0;
-}
 // one state call: checks, ordering, list, kernels (to_records: export), optional copies of the host variants
 static int ss_call(nnn_batch *h, SsOp op, const int *streams, int n, const void *host_src, void *host_dst, const void *d_src, void *d_dst,
                    void *hip_stream, bool device_check)
@@ -1261,7 +1266,7 @@ static int ss_call(nnn_batch *h, SsOp op, const int *streams, int n, const void 
     if (n == 0) return 0;
     if (int rc = ss_prepare(h)) return rc;
     const size_t bytes = (size_t)n * NNN_STREAM_STATE_BYTES;
-    if ((host_src || host_dst) && ss_stage(h, bytes)) return 1;
+    if ((host_src || host_dst) && bytes > h->ss_stage.cap && grow(h, false, h->ss_stage, bytes, bytes)) return 1;   // (no drain: host variants wait for their work)
     hipError_t e;
     hipStream_t st = call_begin(h, hip_stream, e);
     if (e != hipSuccess) return fail("could not order the call after the batch's earlier work: %s", hipGetErrorString(hipGetLastError()));
@@ -1269,22 +1274,22 @@ static int ss_call(nnn_batch *h, SsOp op, const int *streams, int n, const void 
     bool tiles = false;
     if (int rc = ss_args(h, streams, n, st, a, tiles)) return rc;
     if (host_src) {
-        HIPCHK(hipMemcpyAsync(h->ss_stage, host_src, bytes, hipMemcpyHostToDevice, st));
-        d_src = h->ss_stage;
+        HIPCHK(hipMemcpyAsync(h->ss_stage.p, host_src, bytes, hipMemcpyHostToDevice, st));
+        d_src = h->ss_stage.p;
     }
     if (device_check) {
         HIPCHK(hipMemsetAsync(h->ss_flag, 0, sizeof(int), st));
         hipLaunchKernelGGL(k_ss_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, (const unsigned *)d_src, h->ss_flag, h->ss_bad_dev);
         a.flag = h->ss_flag;
     }
-    if (op == SS_EXPORT) ss_launch(h, true, a, tiles, nullptr, host_dst ? (void *)h->ss_stage : d_dst, st);
+    if (op == SS_EXPORT) ss_launch(h, true, a, tiles, nullptr, host_dst ? (void *)h->ss_stage.p : d_dst, st);
     else ss_launch(h, false, a, tiles, op == SS_RESET ? nullptr : d_src, nullptr, st);
     bool any_held = false;
     for (int i = 0; i < n && h->n_held > 0 && !any_held; i++) any_held = h->held[(size_t)streams[i]] != 0;
     if (any_held)
         hipLaunchKernelGGL(k_ss_parked, dim3((unsigned)n), dim3(256), 0, st, a, (const unsigned long long *)h->live, h->park, op == SS_EXPORT ? 1 : 0,
-                           (unsigned *)(host_dst ? (void *)h->ss_stage : d_dst), (const unsigned *)(op == SS_IMPORT ? d_src : nullptr));
-    if (host_dst) HIPCHK(hipMemcpyAsync(host_dst, h->ss_stage, bytes, hipMemcpyDeviceToHost, st));
+                           (unsigned *)(host_dst ? (void *)h->ss_stage.p : d_dst), (const unsigned *)(op == SS_IMPORT ? d_src : nullptr));
+    if (host_dst) HIPCHK(hipMemcpyAsync(host_dst, h->ss_stage.p, bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipGetLastError());
     HIPCHK(call_end(h, st));
     h->prev_pipe = false;
@@ -1573,6 +1578,8 @@ static int drain_profile(nnn_batch *h)
     return 0;
 }
 
+constexpr size_t ZC_MAX = (size_t)1 << 20;                 // host-buffer calls up to this many bytes run on mapped host memory (plan_host_call)
+constexpr size_t HOST_CHUNK_MIN_BYTES = (size_t)1 << 20;   // a chunk of a host-buffer call is at least this long
 struct CallPlan {             // what a call decides before it launches anything (plan_call, which reads the batch only)
     std::vector<int> sizes;   // frames of each group
     bool pipe;                // spread over the internal streams (otherwise the groups' stages back to back on the caller's stream)
@@ -1628,6 +1635,65 @@ static CallPlan plan_call(const nnn_batch *h, int n_frames, hipStream_t st)
     // window is too short (57.5 -> 56.3).
     c.hp_after = c.sched == SCHED_LANES && c.lanes == 1 && h->S_pad >= 8192;
     return c;
+}
+
+// How a host-buffer call crosses the bus (plan_host_call, which reads the batch only; process_host_span runs it,
+// nnn_batch_debug_host_plan shows it to the tests)
+enum HostRoute { HOST_ZERO_COPY = 0, HOST_ONE_PIECE = 1, HOST_CHUNKED = 2 };
+struct HostPlan {
+    int route;
+    int chunk, n_chunks;   // frames per chunk and chunks (one chunk of n_frames unless HOST_CHUNKED)
+    size_t span;           // bytes of the bounding span of the (possibly strided) layout: what is shipped
+    size_t vbytes;         // bytes of the VAD rows, 0 = not asked for
+    size_t vofs;           // where the VAD rows sit behind the span in a host image of both (zero-copy; one piece with vad_masked)
+    int drop;              // 1 = the first frame produces no audio (discard_first on a fresh batch)
+    bool vad_masked;       // one piece: the VAD rows come back through the host image too, a held stream's entries are not copied
+};
+static HostPlan plan_host_call(const nnn_batch *h, int n_frames, const nnn_pcm_layout &L, bool has_vad)
+{
+    const size_t e = (size_t)pcm_elem_bytes(L.format), groups = (size_t)(h->S / L.channels), fr = (size_t)FRAME * L.channels * e;
+    HostPlan p;
+    p.route = HOST_ZERO_COPY, p.chunk = n_frames, p.n_chunks = 1;   // (until the rules below say otherwise)
+    p.span = (groups - 1) * L.group_stride * e + (size_t)(n_frames - 1) * L.frame_stride * e + fr;
+    p.vbytes = has_vad ? (size_t)n_frames * h->S * sizeof(float) : 0;
+    p.vofs = (p.span + 15) / 16 * 16;
+    p.drop = (L.discard_first && h->frame_count == 0) ? 1 : 0;
+    p.vad_masked = has_vad && h->n_held > 0;
+    // Small calls -- the RNNoise C ABI's state is a batch of one, a frame per call -- have nothing to overlap and pay for every runtime call they
+    // make: two or three staged copies of a few kilobytes cost more than the three kernels between them.  Up to ZC_MAX bytes the kernels work on
+    // page-locked host memory directly (the input read over the link by the first kernel, audio and VAD written over it by the last): one
+    // memcpy in, one wait, one memcpy out.  Same kernels, same bits.  An explicit NNN_HOST_CHUNK always takes the staged routes.
+    if (h->paths.host_chunk < 0 && p.span + p.vbytes + 16 <= ZC_MAX) return p;
+    // Chunk length.  The first upload and the last download are not overlapped, so a call wants many chunks (about sixteen); the kernels
+    // want groups of a few frames on small batches (a 4096-stream batch runs 4-frame groups at 0.8 of its 24-frame rate, a 65 536-stream
+    // batch is within 15 % of its best on one-frame groups -- and still twice as fast as the bus).  Measured with page-locked buffers
+    // against the link's own both-ways peak of 97 GB/s (profiles/r5_host_boundary.txt): 4096 streams x 48 frames f32 at 4 / 8 / 16-frame
+    // chunks 84 / 79 / 69 GB/s both ways (round 4 used 8), 65 536 x 24 at 1 / 2 / 4 / 8: 90 / 87 / 81 / 71 (int16: 81 / 84 / 77 / 66).
+    // Chunks under a megabyte are not worth their launches.
+    int chunk = h->paths.host_chunk;
+    if (chunk < 0) {
+        constexpr int HC = 16;   // longest chunk
+        chunk = n_frames / 16;
+        if (chunk < 1) chunk = 1;
+        if (h->S_pad <= 8192 && chunk < 4) chunk = 4;
+        if (chunk > HC) chunk = HC;
+        while (chunk < HC && (size_t)chunk * fr * groups < HOST_CHUNK_MIN_BYTES) chunk *= 2;
+        if ((size_t)chunk * fr * groups < HOST_CHUNK_MIN_BYTES) chunk = 0;
+    }
+    // (the chunks' downloads go straight into the caller's buffers, whole rows of every stream: with streams held the call takes the
+    // one-piece route, whose copy back leaves out what a held stream owns)
+    const bool chunked = chunk > 0 && n_frames > chunk && L.frame_stride == (size_t)FRAME * L.channels && !h->n_held;
+    p.route = chunked ? HOST_CHUNKED : HOST_ONE_PIECE;
+    if (chunked) p.chunk = chunk, p.n_chunks = (n_frames + chunk - 1) / chunk;
+    return p;
+}
+// The training host call's chunk length (nnn_train_process_host): 16 frames (tuned on the bus, not tied to the kernels' group length) for
+// calls of more than two such chunks that are worth their launches, otherwise one piece; NNN_HOST_CHUNK (tests) overrides it.
+static int plan_train_chunk(const nnn_batch *h, int n_frames)
+{
+    constexpr int HC = 16;
+    if (const int hc = h->paths.host_chunk; hc >= 0) return hc > 0 && hc < n_frames ? hc : n_frames;
+    return n_frames > 2 * HC && (size_t)h->S * HC * FRAME * 4 >= HOST_CHUNK_MIN_BYTES ? HC : n_frames;
 }
 
 // A call's launches in the order they are enqueued, with the stream each goes on and the events it waits for and records
@@ -1783,15 +1849,9 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
         h->frame_log += (size_t)v0.log_frames * h->S * FRAME_LOG_WORDS;
         h->frame_log_left -= (size_t)v0.log_frames;
     }
-    if (n_frames > h->sp_tab_cap) {
-        NNN_RT_LOCK;
-        if (int rc = quiesce(h)) return rc;
-        if (h->sp_tab) HIPCHK(hipFree(h->sp_tab));
-        h->sp_tab = nullptr;
-        h->sp_tab_cap = 0;
-        const int cap = n_frames < 64 ? 64 : n_frames;
-        HIPCHK(hipMalloc((void **)&h->sp_tab, (size_t)2 * cap * sizeof(StepParams)));
-        h->sp_tab_cap = cap;
+    if ((size_t)n_frames > h->sp_tab.cap) {
+        const size_t cap = n_frames < 64 ? 64 : (size_t)n_frames;
+        if (int rc = grow(h, true, h->sp_tab, 2 * cap * sizeof(StepParams), cap)) return rc;
         h->prev_pipe = false;
     }
     const CallPlan cp = plan_call(h, n_frames, st);
@@ -1799,7 +1859,7 @@ static int process_frames(nnn_batch *h, const void *d_in, void *d_out, float *d_
     const int n_groups = (int)cp.sizes.size();
     h->call_count += 1;
     const int par = (int)(h->call_count & 1);
-    StepParams *const tab = h->sp_tab + (size_t)par * h->sp_tab_cap;   // this call's parameter table
+    StepParams *const tab = h->sp_tab.p + (size_t)par * h->sp_tab.cap;   // this call's parameter table
     const uint64_t frame0 = h->frame_count;
     bool ok = true;
     if (sc.fill != FILL_FOLDED) {
@@ -1880,66 +1940,72 @@ extern "C" int nnn_batch_process_pcm_device(nnn_batch *h, const void *d_in, void
                           (long long)L->frame_stride * e, drop, hip_stream);
 }
 
-// the two copy streams of chunked host calls and an (uploaded, processed) event pair per chunk, made on first use
-static int host_copy_streams(nnn_batch *h, int n_chunks)
+// Chunked host calls (the denoiser's and the training rows'): chunk i + 1 crosses the bus on one copy stream while chunk i is processed on
+// the batch's stream and chunk i - 1 returns on another (PCIe is full duplex).  upload(t0, n) enqueues n frames from t0 on copy_in,
+// run(t0, n) processes them on h->stream, download(t0, n) enqueues what comes back on copy_out.  Nothing more is enqueued after the
+// first error; all three streams are drained either way.  The copy streams and an event pair per chunk are made on first use.
+template <class Up, class Run, class Down> static int pump_chunks(nnn_batch *h, int n_frames, int C, Up upload, Run run, Down download)
 {
-    if (h->copy_in && (int)h->ev_up.size() >= n_chunks) return 0;
-    NNN_RT_LOCK;
-    if (!h->copy_in) {
-        HIPCHK(hipStreamCreateWithFlags(&h->copy_in, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&h->copy_out, hipStreamNonBlocking));
-    }
-    while ((int)h->ev_up.size() < n_chunks) {
-        hipEvent_t a, b;
-        HIPCHK(hipEventCreateWithFlags(&a, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&b, hipEventDisableTiming));
-        h->ev_up.push_back(a);
-        h->ev_run.push_back(b);
-    }
-    return 0;
-}
-
-// A long host-buffer call with gap-free frames runs in chunks of C frames: chunk i + 1 crosses the bus on one copy
-// stream while chunk i is processed and chunk i - 1 returns on another (PCIe is full duplex), every transfer a 2-D copy of
-// groups x chunk-bytes straight between the caller's buffers and the device staging (DMA when they are page-locked --
-// nnn_host_alloc -- and staged by the runtime when not).  The device staging has the layout of the host buffers.
-static int process_host_chunked(nnn_batch *h, const char *in, char *out, float *vad, int n_frames, const nnn_pcm_layout *L, char *d, float *dv,
-                                int drop, int C)
-{
-    const size_t e = (size_t)pcm_elem_bytes(L->format), groups = (size_t)(h->S / L->channels), fr = (size_t)FRAME * L->channels * e;
-    const size_t pitch = groups > 1 ? L->group_stride * e : (size_t)n_frames * fr;
     const int nch = (n_frames + C - 1) / C;
-    if (int rc = host_copy_streams(h, nch)) return rc;
+    if (!h->copy_in || (int)h->ev_up.size() < nch) {
+        NNN_RT_LOCK;
+        if (!h->copy_in) {
+            HIPCHK(hipStreamCreateWithFlags(&h->copy_in, hipStreamNonBlocking));
+            HIPCHK(hipStreamCreateWithFlags(&h->copy_out, hipStreamNonBlocking));
+        }
+        while ((int)h->ev_up.size() < nch) {
+            hipEvent_t a, b;
+            HIPCHK(hipEventCreateWithFlags(&a, hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&b, hipEventDisableTiming));
+            h->ev_up.push_back(a);
+            h->ev_run.push_back(b);
+        }
+    }
     // (the previous call ended with every stream drained, so the staging is free)
-    nnn_pcm_layout Lc = *L;
     int rc = 0;
     hipError_t err = hipSuccess;
     for (int i = 0; i < nch && !rc && err == hipSuccess; i++) {
-        const int t0 = i * C, t1 = t0 + C < n_frames ? t0 + C : n_frames;
-        const size_t off = (size_t)t0 * fr, w = (size_t)(t1 - t0) * fr;
-        err = hipMemcpy2DAsync(d + off, pitch, in + off, pitch, w, groups, hipMemcpyHostToDevice, h->copy_in);
+        const int t0 = i * C, n = t0 + C < n_frames ? C : n_frames - t0;
+        err = upload(t0, n);
         if (err == hipSuccess) err = hipEventRecord(h->ev_up[i], h->copy_in);
         if (err == hipSuccess) err = hipStreamWaitEvent(h->stream, h->ev_up[i], 0);
         if (err != hipSuccess) break;
-        // with a dropped first frame every output sits one frame earlier than its input: chunk i then writes frames
-        // t0 - 1 .. t1 - 2, in place behind inputs that chunk i - 1 has consumed (same stream), and returns those
-        const int o0 = t0 ? t0 - drop : 0, o1 = t1 - drop;
-        rc = nnn_batch_process_pcm_device(h, d + off, d + (size_t)o0 * fr, dv ? dv + (size_t)t0 * h->S : nullptr, t1 - t0, &Lc, h->stream);
+        rc = run(t0, n);
         if (rc) break;
         err = hipEventRecord(h->ev_run[i], h->stream);
         if (err == hipSuccess) err = hipStreamWaitEvent(h->copy_out, h->ev_run[i], 0);
-        if (err == hipSuccess && o1 > o0)
-            err = hipMemcpy2DAsync(out + (size_t)o0 * fr, pitch, d + (size_t)o0 * fr, pitch, (size_t)(o1 - o0) * fr, groups, hipMemcpyDeviceToHost,
-                                   h->copy_out);
-        if (err == hipSuccess && vad)
-            err = hipMemcpyAsync(vad + (size_t)t0 * h->S, dv + (size_t)t0 * h->S, (size_t)(t1 - t0) * h->S * sizeof(float), hipMemcpyDeviceToHost,
-                                 h->copy_out);
+        if (err == hipSuccess) err = download(t0, n);
     }
     const hipError_t e1 = hipStreamSynchronize(h->copy_in), e2 = hipStreamSynchronize(h->stream), e3 = hipStreamSynchronize(h->copy_out);
     if (rc) return rc;
     if (err == hipSuccess) err = e1 != hipSuccess ? e1 : (e2 != hipSuccess ? e2 : e3);
     if (err != hipSuccess) return fail("host transfer failed: %s", hipGetErrorString(err));
-    return nnn_batch_synchronize(h);   // (also reports a frame hand-off that never arrived)
+    return 0;
+}
+
+// A long host-buffer call with gap-free frames runs in chunks of p.chunk frames, every transfer a 2-D copy of groups x chunk-bytes
+// straight between the caller's buffers and the device staging (DMA when they are page-locked -- nnn_host_alloc -- and staged by the
+// runtime when not).  The device staging has the layout of the host buffers.
+static int process_host_chunked(nnn_batch *h, const char *in, char *out, float *vad, int n_frames, const nnn_pcm_layout *L, const HostPlan &p)
+{
+    const size_t e = (size_t)pcm_elem_bytes(L->format), groups = (size_t)(h->S / L->channels), fr = (size_t)FRAME * L->channels * e;
+    const size_t pitch = groups > 1 ? L->group_stride * e : (size_t)n_frames * fr, S = (size_t)h->S;
+    char *const d = h->stage.p;
+    float *const dv = vad ? h->stage_vad.p : nullptr;
+    // with a dropped first frame every output sits one frame earlier than its input: a chunk of frames t0 .. t0 + n - 1 then writes frames
+    // t0 - 1 .. t0 + n - 2, in place behind inputs that the chunk before has consumed (same stream), and returns those
+    auto out0 = [&](int t0) { return (size_t)(t0 ? t0 - p.drop : 0); };
+    const int rc = pump_chunks(h, n_frames, p.chunk,
+        [&](int t0, int n) { return hipMemcpy2DAsync(d + t0 * fr, pitch, in + t0 * fr, pitch, n * fr, groups, hipMemcpyHostToDevice, h->copy_in); },
+        [&](int t0, int n) { return nnn_batch_process_pcm_device(h, d + t0 * fr, d + out0(t0) * fr, dv ? dv + t0 * S : nullptr, n, L, h->stream); },
+        [&](int t0, int n) {
+            const size_t o0 = out0(t0), o1 = (size_t)(t0 + n - p.drop);
+            hipError_t err = hipSuccess;
+            if (o1 > o0) err = hipMemcpy2DAsync(out + o0 * fr, pitch, d + o0 * fr, pitch, (o1 - o0) * fr, groups, hipMemcpyDeviceToHost, h->copy_out);
+            if (err == hipSuccess && vad) err = hipMemcpyAsync(vad + t0 * S, dv + t0 * S, n * S * sizeof(float), hipMemcpyDeviceToHost, h->copy_out);
+            return err;
+        });
+    return rc ? rc : nnn_batch_synchronize(h);   // (also reports a frame hand-off that never arrived)
 }
 
 // The copies back of the host-buffer calls: the frames the call wrote, from a host image `src` of the device buffer into the caller's.
@@ -1969,107 +2035,56 @@ static void host_vad_back(const nnn_batch *h, float *vad, const float *src, int 
             if (!h->held[(size_t)s]) vad[(size_t)t * h->S + s] = src[(size_t)t * h->S + s];
 }
 
-// Host buffers: ship the bounding span of the (possibly strided) layout, run, bring the written frames back.
-static int process_host_span_impl(nnn_batch *h, const void *in, void *out, float *vad, int n_frames, const nnn_pcm_layout *L);
+// Host buffers: ship the bounding span of the (possibly strided) layout, run, bring the written frames back, by plan_host_call's route.
 static int process_host_span(nnn_batch *h, const void *in, void *out, float *vad, int n_frames, const nnn_pcm_layout *L)
 {
+    struct InHostCall {   // (nnn_batch::host_call, until the call returns)
+        nnn_batch *h;
+        ~InHostCall() { h->host_call = false; }
+    } in_host_call{h};
     h->host_call = true;
-    const int rc = process_host_span_impl(h, in, out, vad, n_frames, L);
-    h->host_call = false;
-    return rc;
-}
-static int process_host_span_impl(nnn_batch *h, const void *in, void *out, float *vad, int n_frames, const nnn_pcm_layout *L)
-{
     HIPCHK(hipSetDevice(h->device));
-    const size_t e = (size_t)pcm_elem_bytes(L->format), groups = (size_t)(h->S / L->channels), fr = (size_t)FRAME * L->channels * e;
-    const size_t span = (groups - 1) * L->group_stride * e + (size_t)(n_frames - 1) * L->frame_stride * e + fr;
-    const int drop = (L->discard_first && h->frame_count == 0) ? 1 : 0;
-    const size_t vbytes = vad ? (size_t)n_frames * h->S * sizeof(float) : 0;
-    // Small calls -- the RNNoise C ABI's state is a batch of one, a frame per call -- have nothing to overlap and pay for every runtime call they
-    // make: two or three staged copies of a few kilobytes cost more than the three kernels between them.  Up to ZC_MAX bytes the kernels work on
-    // page-locked host memory directly (the input read over the link by the first kernel, audio and VAD written over it by the last): one
-    // memcpy in, one wait, one memcpy out.  Same kernels, same bits.  An explicit NNN_HOST_CHUNK always takes the staged path below.
-    constexpr size_t ZC_MAX = (size_t)1 << 20;
-    if (h->paths.host_chunk < 0 && span + vbytes + 16 <= ZC_MAX) {
-        const size_t vofs = (span + 15) / 16 * 16;
-        if (!h->zc_host) {
+    const HostPlan p = plan_host_call(h, n_frames, *L, vad != nullptr);
+    if (p.route == HOST_ZERO_COPY) {
+        if (!h->zc_dev) {   // (first use, or an earlier one that failed half-way: zc_dev is set last, and is what says that both exist)
             NNN_RT_LOCK;
-            if (int rc = quiesce(h)) return rc;
-            void *hp = nullptr, *dp = nullptr;
-            HIPCHK(hipHostMalloc(&hp, ZC_MAX, hipHostMallocMapped));
-            HIPCHK(hipHostGetDevicePointer(&dp, hp, 0));
-            h->zc_host = (char *)hp;
-            h->zc_dev = (char *)dp;
-            h->zc_cap = ZC_MAX;
+            if (int rc = grow(h, true, h->zc_host, ZC_MAX, ZC_MAX)) return rc;
+            HIPCHK(hipHostGetDevicePointer((void **)&h->zc_dev, h->zc_host.p, 0));
         }
-        memcpy(h->zc_host, in, span);
-        int rc = nnn_batch_process_pcm_device(h, h->zc_dev, h->zc_dev, vad ? (float *)(h->zc_dev + vofs) : nullptr, n_frames, L, h->stream);
+        memcpy(h->zc_host.p, in, p.span);
+        int rc = nnn_batch_process_pcm_device(h, h->zc_dev, h->zc_dev, vad ? (float *)(h->zc_dev + p.vofs) : nullptr, n_frames, L, h->stream);
         if (!rc) rc = nnn_batch_synchronize(h);   // (also reports a frame hand-off that never arrived)
         else hipStreamSynchronize(h->stream);
         if (!rc) {
-            host_frames_back(h, (char *)out, h->zc_host, L, n_frames - drop);
-            if (vad) host_vad_back(h, vad, (const float *)(h->zc_host + vofs), n_frames);
+            host_frames_back(h, (char *)out, h->zc_host.p, L, n_frames - p.drop);
+            if (vad) host_vad_back(h, vad, (const float *)(h->zc_host.p + p.vofs), n_frames);
         }
         return rc;
     }
-    // device staging grows as needed and is kept for the next call (per-call hipMalloc / hipFree cost more than a frame)
-    if (span > h->stage_cap || vbytes > h->stage_vad_cap) {
-        NNN_RT_LOCK;
+    if (p.span > h->stage.cap || p.vbytes > h->stage_vad.cap) {   // the staging grows by half as much again as is asked for (the VAD rows: twice)
+        NNN_RT_LOCK;   // (one lock and one drain for both)
         if (int rc = quiesce(h)) return rc;
-        if (span > h->stage_cap) {
-            if (h->stage) HIPCHK(hipFree(h->stage));
-            h->stage = nullptr;
-            h->stage_cap = 0;
-            const size_t want = span + span / 2;
-            HIPCHK(hipMalloc((void **)&h->stage, want));
-            h->stage_cap = want;
-        }
-        if (vbytes > h->stage_vad_cap) {
-            if (h->stage_vad) HIPCHK(hipFree(h->stage_vad));
-            h->stage_vad = nullptr;
-            h->stage_vad_cap = 0;
-            HIPCHK(hipMalloc((void **)&h->stage_vad, vbytes * 2));
-            h->stage_vad_cap = vbytes * 2;
-        }
+        if (p.span > h->stage.cap && grow(h, false, h->stage, p.span + p.span / 2, p.span + p.span / 2)) return 1;
+        if (p.vbytes > h->stage_vad.cap && grow(h, false, h->stage_vad, 2 * p.vbytes, 2 * p.vbytes)) return 1;
     }
-    char *d = h->stage;
-    float *dv = vad ? h->stage_vad : nullptr;
-    // Chunk length.  The first upload and the last download are not overlapped, so a call wants many chunks (about sixteen); the kernels
-    // want groups of a few frames on small batches (a 4096-stream batch runs 4-frame groups at 0.8 of its 24-frame rate, a 65 536-stream
-    // batch is within 15 % of its best on one-frame groups -- and still twice as fast as the bus).  Measured with page-locked buffers
-    // against the link's own both-ways peak of 97 GB/s (profiles/r5_host_boundary.txt): 4096 streams x 48 frames f32 at 4 / 8 / 16-frame
-    // chunks 84 / 79 / 69 GB/s both ways (round 4 used 8), 65 536 x 24 at 1 / 2 / 4 / 8: 90 / 87 / 81 / 71 (int16: 81 / 84 / 77 / 66).
-    // Chunks under a megabyte are not worth their launches.
-    int chunk = h->paths.host_chunk;
-    if (chunk < 0) {
-        constexpr int HC = 16;   // longest chunk
-        chunk = n_frames / 16;
-        if (chunk < 1) chunk = 1;
-        if (h->S_pad <= 8192 && chunk < 4) chunk = 4;
-        if (chunk > HC) chunk = HC;
-        while (chunk < HC && (size_t)chunk * fr * groups < ((size_t)1 << 20)) chunk *= 2;
-        if ((size_t)chunk * fr * groups < ((size_t)1 << 20)) chunk = 0;
-    }
-    // (the chunks' downloads go straight into the caller's buffers, whole rows of every stream: with streams held the call takes the
-    // one-piece path below, whose copy back leaves out what a held stream owns)
-    if (chunk > 0 && n_frames > chunk && L->frame_stride == (size_t)FRAME * L->channels && !h->n_held)
-        return process_host_chunked(h, (const char *)in, (char *)out, vad, n_frames, L, d, dv, drop, chunk);
-    hipError_t err = hipMemcpyAsync(d, in, span, hipMemcpyHostToDevice, h->stream);
+    if (p.route == HOST_CHUNKED) return process_host_chunked(h, (const char *)in, (char *)out, vad, n_frames, L, p);
+    char *d = h->stage.p;
+    float *dv = vad ? h->stage_vad.p : nullptr;
+    hipError_t err = hipMemcpyAsync(d, in, p.span, hipMemcpyHostToDevice, h->stream);
     int rc = 0;
     if (err != hipSuccess) rc = fail("host staging failed: %s", hipGetErrorString(err));
     if (!rc) rc = nnn_batch_process_pcm_device(h, d, d, dv, n_frames, L, h->stream);
     if (!rc) {
         // `out` may alias `in` and may be strided: bring the span back and copy only real frames
         std::vector<char> &tmp = h->stage_host;
-        const bool vad_masked = vad && h->n_held > 0;   // (the VAD rows through the host image too: a held stream's entries are not copied)
-        const size_t vofs = (span + 15) / 16 * 16;
-        if (tmp.size() < vofs + (vad_masked ? vbytes : 0)) tmp.resize(vofs + (vad_masked ? vbytes : 0));
-        err = hipMemcpyAsync(tmp.data(), d, span, hipMemcpyDeviceToHost, h->stream);
-        if (err == hipSuccess && vad) err = hipMemcpyAsync(vad_masked ? (void *)(tmp.data() + vofs) : (void *)vad, dv, vbytes, hipMemcpyDeviceToHost, h->stream);
+        const size_t image = p.vofs + (p.vad_masked ? p.vbytes : 0);
+        if (tmp.size() < image) tmp.resize(image);
+        err = hipMemcpyAsync(tmp.data(), d, p.span, hipMemcpyDeviceToHost, h->stream);
+        if (err == hipSuccess && vad) err = hipMemcpyAsync(p.vad_masked ? (void *)(tmp.data() + p.vofs) : (void *)vad, dv, p.vbytes, hipMemcpyDeviceToHost, h->stream);
         if (err == hipSuccess) err = hipStreamSynchronize(h->stream);
         if (err == hipSuccess) {
-            host_frames_back(h, (char *)out, tmp.data(), L, n_frames - drop);
-            if (vad_masked) host_vad_back(h, vad, (const float *)(tmp.data() + vofs), n_frames);
+            host_frames_back(h, (char *)out, tmp.data(), L, n_frames - p.drop);
+            if (p.vad_masked) host_vad_back(h, vad, (const float *)(tmp.data() + p.vofs), n_frames);
         }
         if (err != hipSuccess) rc = fail("copy back failed: %s", hipGetErrorString(err));
         if (!rc) rc = nnn_batch_synchronize(h);   // (also reports a frame hand-off that never arrived)
@@ -2301,7 +2316,7 @@ extern "C" int nnn_batch_debug_schedule(nnn_batch *h, int n_frames, int32_t *out
     if (!h || !out) return fail("null argument");
     if (n_frames < 1) return fail("n_frames must be at least 1");
     CallPlan cp = plan_call(h, n_frames, h->stream);
-    if (n_frames > h->sp_tab_cap) cp.early_hp = false;   // (the call would first grow its parameter table, which drains the batch: prev_pipe off)
+    if ((size_t)n_frames > h->sp_tab.cap) cp.early_hp = false;   // (the call would first grow its parameter table, which drains the batch: prev_pipe off)
     const Schedule sc = plan_schedule(h, cp);
     constexpr size_t HEAD = 8, PER_NODE = 8 + 3 * MAX_WAITS;
     if (cap < HEAD + PER_NODE * sc.nodes.size()) return fail("schedule buffer too small: %zu entries needed", HEAD + PER_NODE * sc.nodes.size());
@@ -2317,6 +2332,16 @@ extern "C" int nnn_batch_debug_schedule(nnn_batch *h, int n_frames, int32_t *out
         }
         out += PER_NODE;
     }
+    return 0;
+}
+// Test hook: the route a host-buffer call of n_frames would take now (include/nnn_batch.h).  Plans only.
+extern "C" int nnn_batch_debug_host_plan(nnn_batch *h, int n_frames, const nnn_pcm_layout *L, int has_vad, int64_t out[8])
+{
+    if (!h || !out || n_frames < 1) return fail("null argument or no frames");
+    if (int rc = check_layout(h, L)) return rc;
+    const HostPlan p = plan_host_call(h, n_frames, *L, has_vad != 0);
+    const int64_t v[8] = {p.route, p.chunk, p.n_chunks, (int64_t)p.span, (int64_t)p.vbytes, (int64_t)p.vofs, p.drop, p.vad_masked};
+    memcpy(out, v, sizeof(v));
     return 0;
 }
 extern "C" int nnn_batch_set_back_end(nnn_batch *h, int mode)
@@ -2345,16 +2370,15 @@ extern "C" int nnn_batch_set_schedule(nnn_batch *h, int mode, int lanes)
 // ---- training-feature rows (include/nnn_train.h) ---------------------------------------------------------------------
 struct nnn_train {
     nnn_batch *comb = nullptr, *clean = nullptr, *noise = nullptr;   // three sets of DenoiseFeatures state
-    float *stage = nullptr;          // device staging of the host entry point (grow-only): [signal | noise | combined | vad | rows]
-    int32_t *stage_cut = nullptr;
-    size_t stage_frames = 0;         // frames the staging holds
+    GrowBuf<float> stage;            // device staging of the host entry point: [signal | noise | combined | vad | rows], capacity in frames
+    GrowBuf<int32_t> stage_cut;
 };
 
 extern "C" void nnn_train_destroy(nnn_train *t)
 {
     if (!t) return;
-    if (t->stage) hipFree(t->stage);
-    if (t->stage_cut) hipFree(t->stage_cut);
+    t->stage.release();
+    t->stage_cut.release();
     nnn_batch_destroy(t->comb);
     nnn_batch_destroy(t->clean);
     nnn_batch_destroy(t->noise);
@@ -2393,7 +2417,7 @@ static void enqueue_feature_group(nnn_batch *h, hipStream_t st, const float *in,
     // kernels cover the group in one launch, the per-frame feature stage once per frame
     const Buffers &b = h->b[0];
     const unsigned NT = (unsigned)h->NT, Sp = (unsigned)h->S_pad, ug = (unsigned)g;
-    StepParams *sp = h->sp_tab;
+    StepParams *sp = h->sp_tab.p;
     StepParams v;
     v.in = (const char *)in;
     v.out = nullptr;
@@ -2459,55 +2483,31 @@ extern "C" int nnn_train_process_host(nnn_train *t, const float *signal, const f
     nnn_batch *h = t->comb;
     HIPCHK(hipSetDevice(h->device));
     const size_t S = (size_t)h->S, na = S * n_frames * FRAME, nl = S * n_frames;
-    if ((size_t)n_frames > t->stage_frames) {   // the staging grows as needed and is kept (per-call hipMalloc / hipFree cost more than a group)
-        NNN_RT_LOCK;
-        if (int rc = quiesce(h)) return rc;
-        if (t->stage) HIPCHK(hipFree(t->stage));
-        if (t->stage_cut) HIPCHK(hipFree(t->stage_cut));
-        t->stage = nullptr;
-        t->stage_cut = nullptr;
-        t->stage_frames = 0;
-        HIPCHK(hipMalloc((void **)&t->stage, (3 * na + nl + nl * TRAIN_COLS) * sizeof(float)));
-        HIPCHK(hipMalloc((void **)&t->stage_cut, nl * sizeof(int32_t)));
-        t->stage_frames = (size_t)n_frames;
-    }
-    float *d = t->stage, *dv = d + 3 * na, *dr = dv + nl;
-    int32_t *dc = t->stage_cut;
-    // Like the denoiser's host calls (process_host_chunked): chunk i + 1 crosses the bus while chunk i is turned into rows and
-    // chunk i - 1's rows return.  Audio is [stream][frame][480] (a chunk: 2-D copies, one row per stream), labels and rows are
-    // frame-major (a chunk: one run each).
-    constexpr int HC = 16;   // frames per chunk (tuned on the bus, not tied to the kernels' group length)
-    int C = n_frames > 2 * HC && S * HC * FRAME * 4 >= ((size_t)1 << 20) ? HC : n_frames;
-    if (h->paths.host_chunk >= 0) C = h->paths.host_chunk > 0 && h->paths.host_chunk < n_frames ? h->paths.host_chunk : n_frames;   // NNN_HOST_CHUNK (tests)
-    const int nch = (n_frames + C - 1) / C;
-    if (int rc = host_copy_streams(h, nch)) return rc;
+    if ((size_t)n_frames > t->stage.cap && grow(h, true, t->stage, (3 * na + nl + nl * TRAIN_COLS) * sizeof(float), (size_t)n_frames, &t->stage_cut, nl * sizeof(int32_t))) return 1;
+    float *d = t->stage.p, *dv = d + 3 * na, *dr = dv + nl;
+    int32_t *dc = t->stage_cut.p;
+    // In chunks like the denoiser's host calls.  Audio is [stream][frame][480] (a chunk: 2-D copies, one row per stream), labels and rows
+    // are frame-major (a chunk: one run each).
     const size_t pitch = (size_t)n_frames * FRAME * 4;
     const float *src[3] = {signal, noise, combined};
-    int rc = 0;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < nch && !rc && e == hipSuccess; i++) {
-        const int t0 = i * C, n = t0 + C < n_frames ? C : n_frames - t0;
-        const size_t off = (size_t)t0 * FRAME, lo = (size_t)t0 * S;
-        for (int k = 0; k < 3 && e == hipSuccess; k++)
-            e = hipMemcpy2DAsync(d + k * na + off, pitch, src[k] + off, pitch, (size_t)n * FRAME * 4, S, hipMemcpyHostToDevice, h->copy_in);
-        if (e == hipSuccess) e = hipMemcpyAsync(dv + lo, vad + lo, (size_t)n * S * 4, hipMemcpyHostToDevice, h->copy_in);
-        if (e == hipSuccess) e = hipMemcpyAsync(dc + lo, cutoff + lo, (size_t)n * S * 4, hipMemcpyHostToDevice, h->copy_in);
-        if (e == hipSuccess) e = hipEventRecord(h->ev_up[i], h->copy_in);
-        if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->ev_up[i], 0);
-        if (e != hipSuccess) break;
-        rc = nnn_train_process_device(t, d + off, d + na + off, d + 2 * na + off, dc + lo, dv + lo, dr + lo * TRAIN_COLS, n,
-                                      (size_t)n_frames * FRAME, FRAME, h->stream);
-        if (rc) break;
-        e = hipEventRecord(h->ev_run[i], h->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(h->copy_out, h->ev_run[i], 0);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(rows + lo * TRAIN_COLS, dr + lo * TRAIN_COLS, (size_t)n * S * TRAIN_COLS * 4, hipMemcpyDeviceToHost, h->copy_out);
-    }
-    const hipError_t e1 = hipStreamSynchronize(h->copy_in), e2 = hipStreamSynchronize(h->stream), e3 = hipStreamSynchronize(h->copy_out);
-    if (rc) return rc;
-    if (e == hipSuccess) e = e1 != hipSuccess ? e1 : (e2 != hipSuccess ? e2 : e3);
-    if (e != hipSuccess) return fail("host transfer failed: %s", hipGetErrorString(e));
-    return 0;
+    return pump_chunks(h, n_frames, plan_train_chunk(h, n_frames),
+        [&](int t0, int n) {
+            const size_t off = (size_t)t0 * FRAME, lo = (size_t)t0 * S;
+            hipError_t e = hipSuccess;
+            for (int k = 0; k < 3 && e == hipSuccess; k++)
+                e = hipMemcpy2DAsync(d + k * na + off, pitch, src[k] + off, pitch, (size_t)n * FRAME * 4, S, hipMemcpyHostToDevice, h->copy_in);
+            if (e == hipSuccess) e = hipMemcpyAsync(dv + lo, vad + lo, n * S * 4, hipMemcpyHostToDevice, h->copy_in);
+            if (e == hipSuccess) e = hipMemcpyAsync(dc + lo, cutoff + lo, n * S * 4, hipMemcpyHostToDevice, h->copy_in);
+            return e;
+        },
+        [&](int t0, int n) {
+            const size_t off = (size_t)t0 * FRAME, lo = (size_t)t0 * S;
+            return nnn_train_process_device(t, d + off, d + na + off, d + 2 * na + off, dc + lo, dv + lo, dr + lo * TRAIN_COLS, n,
+                                            (size_t)n_frames * FRAME, FRAME, h->stream);
+        },
+        [&](int t0, int n) {
+            return hipMemcpyAsync(rows + t0 * S * TRAIN_COLS, dr + t0 * S * TRAIN_COLS, n * S * TRAIN_COLS * 4, hipMemcpyDeviceToHost, h->copy_out);
+        });
 }
 
 // ---- model entry points -------------------------------------------------------------------------

@@ -417,6 +417,25 @@ def test_interleaved_formats_match_planar(nn):
     assert np.abs(out - np.clip(want / np.float32(32768.0), -1, 1)).max() <= 1e-6
 
 
+def _host_plan(nn, bd, n_frames):
+    """(route, frames per chunk, chunks, ...) of a contiguous f32 mono host call with VAD, as nnn_batch_debug_host_plan gives it:
+    route 0 = zero-copy, 1 = one piece, 2 = chunked."""
+    import ctypes as C
+    from nnnoiseless_amd import _ffi
+    lay = _ffi.PcmLayout(_ffi.PCM_F32, 1, 0, 0, n_frames * 480, 480)
+    out = (C.c_int64 * 8)()
+    bd._lib.check(bd._lib.L.nnn_batch_debug_host_plan(bd._h, n_frames, C.byref(lay), 1, out))
+    return tuple(out)
+
+
+def test_host_plan_of_a_very_large_batch(nn, monkeypatch):
+    """Above 8192 streams a chunk has no four-frame minimum: 16 384 streams (sized for one-frame groups, 33 KB per stream) x 24 frames
+    go in 24 chunks of one frame, 24 / 16 = 1, whose 1920 * 16 384 bytes are far over a megabyte.  Plans only: no frame runs."""
+    monkeypatch.delenv("NNN_HOST_CHUNK", raising=False)
+    bd = nn.BatchDenoiser(16384, max_group_frames=1)
+    assert _host_plan(nn, bd, 24)[:3] == (2, 1, 24)
+
+
 def test_host_calls_in_chunks_and_pinned_buffers(nn, monkeypatch):
     """Host-buffer calls of more than 16 frames cross the bus in chunks, uploads and downloads beside the kernels: same bits as
     the one-piece call, from pageable and from page-locked arrays, planar f32 and packed int16 stereo with the dropped frame."""
@@ -430,12 +449,14 @@ def test_host_calls_in_chunks_and_pinned_buffers(nn, monkeypatch):
     ref, vref = bd.process(x)
     bd.reset()
     iref, ivref = bd.process_pcm(inter, _ffi.PCM_I16, 2, discard_first=True)
-    for chunk in (None, "16", "8"):   # None: the library's own choice (4-frame chunks for a call of 40 frames)
+    for chunk in (None, "16", "8"):   # None: the library's own choice
         if chunk is None:
             monkeypatch.delenv("NNN_HOST_CHUNK")
         else:
             monkeypatch.setenv("NNN_HOST_CHUNK", chunk)
         bd = nn.BatchDenoiser(S)
+        if chunk is None:   # 40 / 16 = 2 frames, at least 4 up to 8192 streams; 4 * 1920 * 454 bytes are over a megabyte
+            assert _host_plan(nn, bd, T)[:3] == (2, 4, 10)
         out, vad = bd.process(x)
         assert np.array_equal(out, ref) and np.array_equal(vad, vref), chunk
         px, po, pv = nn.pinned_empty(x.shape), nn.pinned_empty(x.shape), nn.pinned_empty((T, S))
