@@ -8,7 +8,8 @@ Host-side mirror of the reference's public interface for this path (jneem/nnnois
   BatchDenoiser n independent DenoiseStates advanced in lock-step (the per-channel loop of
                 src/signal.rs:102-104 and src/nnnoiseless.rs:318-320 as one call)
 
-All arithmetic runs in hand-written HIP kernels (csrc/nnn_kernels.hip) behind the C ABI of
+All arithmetic runs in hand-written HIP kernels (csrc/nnn_kernels.hip and the stage files it
+includes, one per stage: nnn_hp.hip ... nnn_synth.hip) behind the C ABI of
 include/nnn_batch.h and include/rnnoise.h.  There is no CPU fallback: importing works anywhere,
 but creating a state without the built library or without a GPU raises.
 """

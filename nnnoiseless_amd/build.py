@@ -31,12 +31,13 @@ def build_library(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value", "-I", CSRC,
               f'-DNNN_WEIGHTS_PATH="{WEIGHTS}"']
-    # the two high-pass kernels in a unit of their own, with the SLP pairing the rest of the library is built without (nnn_kernels.hip, at k_hp2)
+    # the two high-pass kernels in a unit of their own (nnn_hp.hip with nnn_common.hip: NNN_HP_UNIT makes it emit them), with the SLP pairing
+    # the rest of the library is built without (nnn_hp.hip, at k_hp2); the stage file is the unit's main file, hence the #pragma once warning off
     # (per-process temporaries, the library moved into place at the end: two builds at once -- a test run beside a manual build -- do not
     # see each other's half-written files)
     hp_obj = os.path.join(LIB_DIR, f"nnn_hp.{os.getpid()}.o")
     tmp_lib = os.path.join(LIB_DIR, f"libnnnoiseless_mi355x.{os.getpid()}.so")
-    cmds = [common + ["-c", "-x", "hip", os.path.join(CSRC, HP_SOURCE), "-o", hp_obj],
+    cmds = [common + ["-DNNN_HP_UNIT", "-Wno-pragma-once-outside-header", "-c", "-x", "hip", os.path.join(CSRC, HP_SOURCE), "-o", hp_obj],
             common + ["-fno-slp-vectorize", "-DNNN_HP_EXTERN", "-shared", "-x", "hip"] + [os.path.join(CSRC, s) for s in SOURCES]
             + ["-x", "none", hp_obj, "-o", tmp_lib]]
     try:

@@ -1,5 +1,6 @@
+#pragma once
 // nnn_pitch.hip -- the pitch stage: k_pitch and everything only it uses.  Not a translation unit: nnn_kernels.hip includes it between the LPC
-// kernels and the transforms.  lpc_finish, which k_lpc shares, stays there; xt_rider's definition stays with the transforms.
+// kernels (nnn_lpc.hip) and the transforms (nnn_fft.hip).  lpc_finish, which k_lpc shares, stays in nnn_lpc.hip; xt_rider's definition in nnn_fft.hip.
 //
 // ---------------------------------------------------------------------------------------------
 // K3  pitch: the pitch analysis of a frame from the FIR on, one block per 16 consecutive streams (a quarter tile):
@@ -33,6 +34,8 @@
 //     remove_doubling carries last_period / last_gain from frame to frame: the launch loops over the `g` frames of its
 //     group; the next frame's decimated window is requested a frame ahead and waits in registers.
 // ---------------------------------------------------------------------------------------------
+namespace nnn {
+
 constexpr int PK_SPB = 16;                       // streams per block
 constexpr int PK_WAVES = 8;
 constexpr int PK_T = 64 * PK_WAVES;
@@ -1406,3 +1409,5 @@ __global__ void __launch_bounds__(PK_T, NNN_PK_MINWAVES) k_pitch(Buffers b, cons
         NNN_TI(b.last_gain, 1, tile, q0 + s)[0] = last_gain;
     }
 }
+
+}  // namespace nnn

@@ -2,13 +2,15 @@
 """Instruction counts of one kernel by basic block and source-line range, from device assembly built with -g (.loc directives):
 which loop of the source a run of instructions belongs to, and how many vector / LDS / scalar instructions it holds -- multiply by the
 loop's trip count (known from the source) for the dynamic count.  usage: isa_by_line.py kg.s kernel_symbol_substring [src_file_substring]
-(src_file_substring defaults to nnn_kernels.hip; the pitch stage -- k_pitch and its helpers -- is nnn_pitch.hip: pass that for k_pitch)"""
+Line numbers are those of ONE source file: by default the file that defines the kernel (the first .loc behind its label), its stage file
+(csrc/nnn_hp.hip, nnn_lpc.hip, nnn_pitch.hip, nnn_fft.hip, nnn_features.hip, nnn_rnn.hip, nnn_rnn_wf.hip, nnn_synth.hip, nnn_back.hip,
+nnn_stream_state.hip; nnn_kernels.hip only includes them).  Pass another to follow what a kernel inlines from it, e.g. k_synth nnn_fft.hip."""
 import collections
 import re
 import sys
 
 path, kname = sys.argv[1], sys.argv[2]
-srcsub = sys.argv[3] if len(sys.argv) > 3 else "nnn_kernels.hip"
+srcsub = sys.argv[3] if len(sys.argv) > 3 else None
 lines = open(path).read().split("\n")
 files = {}
 for l in lines:
@@ -28,13 +30,17 @@ for l in lines[start + 1:end + 1]:
         continue
     m = re.match(r"\s+\.loc\s+(\d+)\s+(\d+)", l)
     if m:
-        f = files.get(int(m.group(1)), "")
-        loc = int(m.group(2)) if srcsub in f else -int(m.group(2))
+        loc = (files.get(int(m.group(1)), ""), int(m.group(2)))
         continue
     m = re.match(r"\s+([a-z_0-9]+)", l)
     if m and not l.strip().startswith(".") and not l.strip().startswith(";"):
         cur[1].append((m.group(1), loc, l))
 blocks.append(cur)
+if srcsub is None:
+    srcsub = next(loc[0] for lab, ins in blocks for op, loc, raw in ins if loc)
+print("source lines of", srcsub)
+# (lines of the other files negative: counted in the histogram, left out of a loop's line range)
+blocks = [(lab, [(op, loc and (loc[1] if srcsub in loc[0] else -loc[1]), raw) for op, loc, raw in ins]) for lab, ins in blocks]
 label_idx = {b[0]: i for i, b in enumerate(blocks)}
 # loops: a backward branch from block j to label at index i <= j
 loops = []
