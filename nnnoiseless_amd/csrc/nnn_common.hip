@@ -77,7 +77,9 @@ __device__ __forceinline__ void xcd_tile_block_units(int blk, int ntiles, int bp
 #else
 #define NNN_CONSTANT __constant__   // (the tests' interpreter build defines __constant__ as static)
 #endif
-NNN_CONSTANT int kEband[NB] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 34, 40, 48, 60, 78, 100};
+#define NNN_EBAND {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 34, 40, 48, 60, 78, 100}
+NNN_CONSTANT int kEband[NB] = NNN_EBAND;
+constexpr int kEbandHost[NB] = NNN_EBAND;   // the same edges for host code (the tables of creation): kEband is a device symbol
 NNN_CONSTANT int kSecondCheck[16] = {0, 0, 3, 2, 3, 2, 5, 2, 3, 2, 3, 2, 5, 2, 3, 2};
 
 // ---- PCM formats at the boundary ------------------------------------------------------------------

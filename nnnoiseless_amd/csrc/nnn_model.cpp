@@ -1,10 +1,16 @@
 // nnn_model.cpp -- .rnn model container: parser with the reference's validation rules, the
-// built-in weights, and the packing the RNN kernels consume (bf16 weights in MFMA B-fragment order, f32 biases).
+// built-in weights, the packing the RNN kernels consume (bf16 weights in MFMA B-fragment order, f32 biases), and the
+// nnn_model_* entry points of include/nnn_batch.h.
 #include "nnn_model.h"
 
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
+
+#include "../../include/nnn_batch.h"
+
+int nnn_set_error(const char *msg);   // nnn_batch_core.hip
 
 // The built-in model is the reference's src/weights.rnn (BSD-3-Clause, (c) Mozilla / Xiph / J. Neeman),
 // shipped as data in nnnoiseless_amd/data/weights.rnn and linked in verbatim
@@ -201,4 +207,82 @@ size_t nnn_model_pack(const RNNModel &m, std::vector<uint16_t> &wq, std::vector<
     // dynamic LDS: tanh table (256 floats) + live flags (64 ints) + 3 planes of both matrices + the staged
     // cepstral ring of the feature stage (8 x 22 rows of 64 floats) and its 28 pair distances
     return 256 * 4 + 64 * 4 + (size_t)3 * 64 * (plan.in_w + plan.rec_w) * 2 + (size_t)(8 * 22 + 28) * 64 * 4;
+}
+
+// ---- model entry points -------------------------------------------------------------------------
+extern "C" RNNModel *nnn_model_from_bytes(const uint8_t *bytes, size_t len)
+{
+    RNNModel *m = nnn_model_parse(bytes, len);
+    if (!m) nnn_set_error("malformed .rnn model");
+    return m;
+}
+extern "C" RNNModel *nnn_model_default(void)
+{
+    size_t len;
+    const uint8_t *w = nnn_builtin_weights(&len);
+    return nnn_model_parse(w, len);
+}
+// RNNoise text model -> .rnn bytes (ref: train/convert_rnnoise.py:18-29).  Python's str.strip / str.split / int():
+// ASCII whitespace separators, optional sign, decimal digits (int() also takes '_' separators and non-ASCII digits;
+// no model file uses them and they are rejected here).
+extern "C" long nnn_convert_rnnoise_text(const char *text, size_t len, uint8_t *out, size_t cap)
+{
+    static const char kHeader[] = "rnnoise-nu model file version 1";
+    auto is_ws = [](char c) { return c == ' ' || (c >= '\t' && c <= '\r'); };
+    auto not_an_integer = [](long n) {
+        char msg[64];
+        snprintf(msg, sizeof(msg), "token %ld is not an integer", n);
+        nnn_set_error(msg);
+    };
+    if (!text) { nnn_set_error("null text"); return -1; }
+    size_t eol = 0;
+    while (eol < len && text[eol] != '\n') eol++;
+    size_t a = 0, b = eol;
+    while (a < b && is_ws(text[a])) a++;
+    while (b > a && is_ws(text[b - 1])) b--;
+    if (b - a != sizeof(kHeader) - 1 || memcmp(text + a, kHeader, b - a) != 0) { nnn_set_error("Unexpected input file format"); return -1; }
+    long n = 0;
+    size_t i = eol < len ? eol + 1 : len;
+    while (i < len) {
+        while (i < len && is_ws(text[i])) i++;
+        if (i >= len) break;
+        bool neg = false;
+        if (text[i] == '+' || text[i] == '-') neg = text[i++] == '-';
+        if (i >= len || text[i] < '0' || text[i] > '9') { not_an_integer(n); return -1; }
+        unsigned v = 0;   // only the value modulo 256 matters
+        while (i < len && text[i] >= '0' && text[i] <= '9') v = (v * 10u + (unsigned)(text[i++] - '0')) & 0xffffu;
+        if (i < len && !is_ws(text[i])) { not_an_integer(n); return -1; }
+        const uint8_t byte = (uint8_t)((neg ? 256u - (v & 255u) : v) & 255u);   // Python's non-negative modulo
+        if (out) {
+            if ((size_t)n >= cap) { nnn_set_error("output buffer too small"); return -1; }
+            out[n] = byte;
+        }
+        n++;
+    }
+    return n;
+}
+extern "C" RNNModel *nnn_model_from_rnnoise_text(const char *text, size_t len)
+{
+    const long n = nnn_convert_rnnoise_text(text, len, nullptr, 0);
+    if (n < 0) return nullptr;
+    std::vector<uint8_t> bytes((size_t)n);
+    if (nnn_convert_rnnoise_text(text, len, bytes.data(), bytes.size()) != n) return nullptr;
+    return nnn_model_from_bytes(bytes.data(), bytes.size());
+}
+extern "C" void nnn_model_free(RNNModel *m) { delete m; }
+// RnnModel is Clone in the reference (#[derive(Clone)], src/rnn.rs:54): an independent copy of the parameters
+extern "C" RNNModel *nnn_model_clone(const RNNModel *m)
+{
+    if (!m) {
+        nnn_set_error("null model");
+        return nullptr;
+    }
+    return new RNNModel(*m);
+}
+extern "C" void nnn_model_shape(const RNNModel *m, int32_t s[12])
+{
+    s[0] = m->input_dense.nb_inputs; s[1] = m->input_dense.nb_neurons; s[2] = m->vad_gru.nb_neurons;
+    s[3] = m->noise_gru.nb_neurons; s[4] = m->denoise_gru.nb_neurons; s[5] = m->denoise_output.nb_neurons;
+    s[6] = m->input_dense.activation; s[7] = m->vad_gru.activation; s[8] = m->noise_gru.activation;
+    s[9] = m->denoise_gru.activation; s[10] = m->denoise_output.activation; s[11] = m->vad_output.activation;
 }

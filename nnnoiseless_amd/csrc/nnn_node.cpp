@@ -16,7 +16,7 @@
 
 #include "../../include/nnn_node.h"
 
-int nnn_set_error(const char *msg);   // nnn_batch.hip
+int nnn_set_error(const char *msg);   // nnn_batch_core.hip
 
 // Pins the calling thread to the CPUs local to a device's PCI function ("0-31,128-159" in the kernel's cpulist syntax, from
 // nnn_device_local_cpulist): a worker that stages pageable buffers and enqueues for GPU i should run on the socket GPU i hangs off.
@@ -200,7 +200,7 @@ extern "C" nnn_node *nnn_node_create(const RNNModel *model, int n_streams, const
     // buffers and enqueues for that GPU), then every worker makes its own batch: the thread is pinned BEFORE it allocates and uploads, so the page-locked
     // staging buffers and the tables' host copies come from its GPU's socket.  The creations themselves still run one after another:
     // nnn_batch_create_opts holds the library's runtime lock for its whole length (allocation and legacy-stream copies must not overlap
-    // another thread's stream capture, nnn_batch.hip), so eight devices take eight creations' time.
+    // another thread's stream capture, g_rt_mu in nnn_batch_core.hip), so eight devices take eight creations' time.
     if (n->threads && n_devices > 1)
         for (auto &s : n->shards) {
             s.w = new Worker();
@@ -338,8 +338,8 @@ extern "C" int nnn_node_fault(const nnn_node *n)
 // ---- per-stream state records by node-global index --------------------------------------------------------------------------------
 // The list is split by shard (part k: the shard-local indices, and where each entry sits in the caller's list); every part is checked on
 // its shard before any shard is written.
-int nnn_batch_check_streams(const nnn_batch *h, int op, const int *streams, int n, const void *host_rec, size_t bytes, bool need_buf);   // nnn_batch.hip
-enum { NODE_SS_RESET = 0, NODE_SS_EXPORT = 1, NODE_SS_IMPORT = 2, NODE_SS_HOLD = 3, NODE_SS_RESUME = 4 };   // (nnn_batch.hip's SsOp)
+int nnn_batch_check_streams(const nnn_batch *h, int op, const int *streams, int n, const void *host_rec, size_t bytes, bool need_buf);   // nnn_batch_streams.hip
+enum { NODE_SS_RESET = 0, NODE_SS_EXPORT = 1, NODE_SS_IMPORT = 2, NODE_SS_HOLD = 3, NODE_SS_RESUME = 4 };   // (nnn_batch_streams.hip's SsOp)
 static int node_split(const nnn_node *n, const int *streams, int n_list, std::vector<std::vector<int>> &local, std::vector<std::vector<int>> &at)
 {
     if (!n) return nnn_set_error("null node");

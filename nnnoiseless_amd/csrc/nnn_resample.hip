@@ -12,7 +12,7 @@
 #include "../../include/nnn_resample.h"
 
 extern "C" const char *nnn_last_error(void);
-int nnn_set_error(const char *msg);   // nnn_batch.hip
+int nnn_set_error(const char *msg);   // nnn_batch_core.hip
 
 namespace {
 

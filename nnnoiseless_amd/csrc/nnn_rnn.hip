@@ -333,6 +333,15 @@ __device__ __forceinline__ void features_row(const Buffers &b, int f, int tile, 
 //     while the others are inside frame f's GRU GEMMs (when the layer shapes leave it without a unit).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ int rnn_state_w(const LayerDesc &L) { return 32 * L.rec.ksteps + 8; }
+// dynamic LDS of k_rnn (mirrors its carve-up): tanh table (256 floats) + live flags (2 x 64 ints), 3 bf16 planes of the
+// input matrix, the r * state matrix, the three state matrices and the feature staging for `rows` streams, the cepstral
+// ring and its pair distances ((8 x 22 + 28) x `rows` floats)
+inline size_t rnn_lds_bytes(const RnnPlan &pl, int rows)
+{
+    auto sw = [](const LayerDesc &L) { return (size_t)(32 * L.rec.ksteps + 8); };
+    const size_t cols = (size_t)pl.in_w + pl.rec_w + sw(pl.vad) + sw(pl.noise) + sw(pl.dn) + FS_W;
+    return (256 + 128) * 4 + (size_t)3 * rows * cols * 2 + (size_t)(CEPS_MEM * NB + 28) * rows * 4;
+}
 
 __global__ void __launch_bounds__(64 * RNN_WAVES) k_rnn(Buffers b, RnnPlan pl, const uint4 *__restrict__ Wq,
                                                           const float *__restrict__ fpar, int tile0, int rm, int g)
@@ -353,7 +362,7 @@ __global__ void __launch_bounds__(64 * RNN_WAVES) k_rnn(Buffers b, RnnPlan pl, c
     if (!live_any(b, tile, r0, rm)) return;
     const bool rowl = lane < rm;                           // lane = stream phases: this lane has a row
     const int trow = r0 + (rowl ? lane : 0);               // its row in the tile
-    // ---- LDS carve-up (rnn_lds_bytes on the host mirrors it)
+    // ---- LDS carve-up (rnn_lds_bytes, above the kernel, mirrors it for the host)
     float *tab = lds_raw;
     int *live = (int *)(lds_raw + 256), *live_next = live + 64;
     unsigned short *IN = (unsigned short *)(lds_raw + 256 + 128);

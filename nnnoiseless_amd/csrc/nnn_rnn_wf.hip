@@ -264,6 +264,12 @@ __host__ __device__ constexpr WfPlan wf_plan_of(const RnnPlan &pl)
     return WfPlan{32 * pl.vad.in.ksteps + 8, 32 * pl.noise.in.ksteps + 8, 32 * pl.dn.in.ksteps + 8,
                   32 * pl.vad.rec.ksteps + 8, 32 * pl.noise.rec.ksteps + 8, 32 * pl.dn.rec.ksteps + 8};
 }
+// the layer-pipelined kernel's dynamic LDS (mirrors k_rnn_wf's carve-up)
+inline size_t rnn_wf_lds_bytes(const WfPlan &w)
+{
+    const size_t cols = (size_t)w.w_v + 2 * w.w_n + 3 * w.w_dn + 2 * ((size_t)w.sw_v + w.sw_n + w.sw_dn) + WF_FS_W;
+    return (256 + 128) * 4 + (size_t)3 * WF_ROWS * cols * 2 + (size_t)(CEPS_MEM * NB + 28 + 28) * WF_ROWS * 4;
+}
 // SH: a shape class with a compile-time packing plan (SH::plan(), e.g. BkShapeBuiltin of nnn_back.hip: every model of the built-in
 // layer sizes) or WfShapeAny (the plan comes with the launch).  With a compile-time plan only the six activation kinds are taken from
 // the launch's plan: every stride, column and fragment offset is a constant -- the run-time form keeps some fifty of them in scalar
@@ -300,7 +306,7 @@ __global__ void __launch_bounds__(64 * WF_WAVES, NNN_WF_MINWAVES) k_rnn_wf(Buffe
     const bool rowl = lane0 < rm;
     const int trow = r0 + (rowl ? lane0 : 0);
     NNN_STAMP(b, 50);
-    // ---- LDS carve-up (rnn_wf_lds_bytes on the host mirrors it)
+    // ---- LDS carve-up (rnn_wf_lds_bytes, above the kernel, mirrors it for the host)
     float *tab = lds_raw;
     int *live = (int *)(lds_raw + 256);                  // [8][16]: live flags of frame f at slot f mod 8 (written a tick before the
                                                          // first reader, read until three ticks after)

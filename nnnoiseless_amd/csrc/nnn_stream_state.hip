@@ -1,6 +1,6 @@
 #pragma once
 // nnn_stream_state.hip -- the device side of the per-stream state records: the record's word layout (SS_*), SsArgs, which the host fills, the
-// ss_* helpers and the k_ss_* kernels.  Not a translation unit: nnn_batch.hip includes it under "per-stream state records", ahead of the host
+// ss_* helpers and the k_ss_* kernels.  Not a translation unit: nnn_batch_streams.hip includes it under "per-stream state records", ahead of the host
 // functions that launch these kernels; it sits at global scope there, behind `using namespace nnn`.
 
 constexpr int SS_WORDS = NNN_STREAM_STATE_BYTES / 4;

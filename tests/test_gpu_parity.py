@@ -524,7 +524,7 @@ def test_rnn_rows_per_block_variants(nn, oracle_mod, weights_bytes, rows, monkey
 # ---- batched training-feature rows -----------------------------------------------------------------
 
 def test_rnn_kernels_agree_bit_for_bit(nn, monkeypatch):
-    """One-frame groups on large batches run k_rnn, longer groups k_rnn_wf (nnn_batch.hip plan_group): streams that change
+    """One-frame groups on large batches run k_rnn, longer groups k_rnn_wf (nnn_batch_launch.hip plan_group): streams that change
     kernel from call to call must not notice."""
     from nnnoiseless_amd.synthetic import make_streams
     x = make_streams(32, 454, 9)

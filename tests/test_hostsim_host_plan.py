@@ -1,4 +1,4 @@
-"""The route of a host-buffer call (nnn_batch.hip plan_host_call, read through nnn_batch_debug_host_plan): zero-copy through mapped
+"""The route of a host-buffer call (nnn_batch_host.hip plan_host_call, read through nnn_batch_debug_host_plan): zero-copy through mapped
 memory, staged in one piece, or staged in chunks over two copy streams -- and the chunk length.  Plans only: no frame runs here.
 
 The expected values are worked out by hand from the rule (include/nnn_batch.h, nnn_batch_process_host):

@@ -25,10 +25,16 @@ def test_developer_knobs_are_not_in_the_product_build():
     import os
     import re
     from nnnoiseless_amd.build import CSRC, LIB_PATH
-    src = open(os.path.join(CSRC, "nnn_batch.hip")).read()
-    product = set(re.findall(r'\bknob\("(NNN_[A-Z_0-9]+)"\)', src))
-    product |= set(re.findall(r'getenv\("(NNN_[A-Z_0-9]+)"\)', open(os.path.join(CSRC, "nnn_node.cpp")).read()))
-    product |= set(re.findall(r'getenv\("(NNN_[A-Z_0-9]+)"\)', open(os.path.join(CSRC, "rnnoise_capi.cpp")).read()))
+    # every source and header of csrc/ (the batch's host side is several part files).  nnn_node.cpp and rnnoise_capi.cpp read their one
+    # variable with getenv itself: those reads are collected into `product` here, every other file's text goes into `src`
+    direct = ("nnn_node.cpp", "rnnoise_capi.cpp")
+    text = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".cpp", ".h"))}
+    assert len(text) > len(direct) and all(f in text for f in direct)
+    src = "\n".join(t for f, t in text.items() if f not in direct)
+    product = set(re.findall(r'\bknob\("(NNN_[A-Z_0-9]+)"\)', "\n".join(text.values())))
+    assert not any(re.findall(r'dev_knob\("', text[f]) for f in direct)
+    product |= set(re.findall(r'getenv\("(NNN_[A-Z_0-9]+)"\)', text["nnn_node.cpp"]))
+    product |= set(re.findall(r'getenv\("(NNN_[A-Z_0-9]+)"\)', text["rnnoise_capi.cpp"]))
     header = open(os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "nnn_batch.h")).read()
     table = header[header.index(" * Environment."):header.index("Earlier rounds' A/B probe knobs")]
     assert product == set(re.findall(r"^ \*   (NNN_[A-Z_0-9]+)", table, re.M)), product     # the table IS the list

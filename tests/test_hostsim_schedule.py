@@ -1,4 +1,4 @@
-"""The stream and event graph of a call (nnn_batch.hip plan_schedule, read through nnn_batch_debug_schedule) orders everything that
+"""The stream and event graph of a call (nnn_batch_launch.hip plan_schedule, read through nnn_batch_debug_schedule) orders everything that
 must be ordered.  The interpreter cannot see a missing edge -- its streams are one stream and its kernels run in issue order -- so
 this file checks the graph itself: for every schedule the hook returns, every required pair (A before B) must follow from stream
 order and from event waits whose event the right node recorded last.
