@@ -222,6 +222,46 @@ int nnn_batch_process_pcm_device(nnn_batch *b, const void *d_in, void *d_out, fl
                                  const nnn_pcm_layout *layout, void *hip_stream);
 int nnn_batch_process_pcm_host(nnn_batch *b, const void *in, void *out, float *vad, int n_frames,
                                const nnn_pcm_layout *layout);
+/*
+ * Split calls: bring your own network.  The reference exports the two halves of process_frame on their own -- DenoiseFeatures
+ * (src/lib.rs:30, src/features.rs:18-275: shift_and_filter_input, compute_frame_features, features(), pitch_filter, the synthesis) and
+ * RnnState::compute (src/rnn.rs:343) -- and process_frame (src/denoise.rs:95-116) is the dozen lines that glue them.  These two calls are
+ * that seam for a batch: ANALYZE runs everything up to the 42 features for up to nnn_batch_max_group_frames(b) consecutive frames of every
+ * stream and hands the rows out; the caller's own network (any size, any framework -- rows are dense f32, a torch model sees [T, S, 42] and
+ * returns [T, S, 22]) turns them into 22 band gains per frame; SYNTHESIZE takes those in place of rnn.compute's and runs the rest.
+ *   d_features[(t * n_streams + s) * 42 + k]       the RNN input of frame t of stream s (all zero on a silent frame)
+ *   d_silence [ t * n_streams + s]                 0 / 1: the frame is digital silence (src/features.rs:160-166)
+ *   d_gains   [(t * n_streams + s) * 22 + band]    used as given: no clamp, a NaN goes where it would in the reference
+ *   d_vad     [ t * n_streams + s]                 optional (NULL reads as 0): the network's VAD, kept only for NNN_TAP_VAD
+ * `layout` describes d_in (analyze) and d_out (synthesize) -- format, channels and strides as nnn_batch_process_pcm_device reads them;
+ * discard_first must be 0 for analyze, synthesize honours it.  Rows are 4-byte aligned.
+ * Analyze = shift_and_filter_input + compute_frame_features: high-pass, LPC, pitch, both transforms with their band energies, the feature
+ * stage.  It advances the input history and biquad state, last_period / last_gain, the cepstral ring and mem_id.  Synthesize, per stream,
+ * frame and band on frames that are not silent: pitch_filter on the caller's gains, g = max(g, 0.6 * lastg), lastg = g, the gains
+ * interpolated and applied; then frame_synthesis.  On silent frames the caller's gains are ignored, lastg stays, VAD is 0 and the synthesis
+ * runs on the unfiltered spectrum, as in the reference.  It advances synthesis_mem and lastg, and the batch's frame count moves here, once
+ * per pair.  Neither call touches the three GRU states: a stream may alternate between split calls and ordinary processing calls, and its
+ * GRU state is what the last ordinary call left.
+ * Protocol: an analyze is followed by a synthesize of the same n_frames before anything else that reads or moves per-stream state.  While
+ * frames are pending (nnn_batch_pending_frames != 0) every processing call, a second analyze, hold / resume, export / import /
+ * reset_streams, clone and save / load_state refuse -- the error text says that frames are pending -- and change nothing;
+ * nnn_batch_reset drops the pending frames; synchronize, fault, the tap reads and destroy work as always.  Refused too, before anything
+ * is enqueued: a synthesize with nothing pending or with another n_frames than was analysed, n_frames outside
+ * [1, nnn_batch_max_group_frames(b)], a NULL required pointer, a bad layout.
+ * The device calls are asynchronous and ordered like processing calls (hip_stream as there: NULL = the batch's own stream); the host
+ * variants stage their buffers in one piece and wait.  Held streams (nnn_batch_hold_streams): analyze does not read their input and
+ * writes neither their feature rows nor their silence entries, synthesize ignores their gains and writes none of their output; live
+ * streams' bits are those of the same calls with nothing held; a pair with every stream held launches nothing and moves the frame count.
+ * With taps on, every tap of the pair's last frame reads after the synthesize as after a processing call; NNN_TAP_G_RAW / NNN_TAP_VAD hold
+ * the caller's values, NNN_TAP_G the smoothed ones.
+ */
+int nnn_batch_analyze_device(nnn_batch *b, const void *d_in, float *d_features, int32_t *d_silence, int n_frames,
+                             const nnn_pcm_layout *layout, void *hip_stream);
+int nnn_batch_synthesize_device(nnn_batch *b, const float *d_gains, const float *d_vad, void *d_out, int n_frames,
+                                const nnn_pcm_layout *layout, void *hip_stream);
+int nnn_batch_analyze_host(nnn_batch *b, const void *in, float *features, int32_t *silence, int n_frames, const nnn_pcm_layout *layout);
+int nnn_batch_synthesize_host(nnn_batch *b, const float *gains, const float *vad, void *out, int n_frames, const nnn_pcm_layout *layout);
+int nnn_batch_pending_frames(const nnn_batch *b);   /* frames analysed and not yet synthesised (0 = none) */
 int nnn_batch_synchronize(nnn_batch *b);
 /* 1 if a pitch workgroup of an earlier call ran out of patience waiting for the previous frame's result (the frames of a group
  * run side by side below 16 384 streams and hand the last pitch from workgroup to workgroup): the state of the affected streams

@@ -139,6 +139,28 @@ class BatchDenoiser {
     {
         check(nnn_batch_process_device(b_.get(), d_in, d_out, d_vad, n_frames, stream_stride, frame_stride, hip_stream));
     }
+    // split calls (nnn_batch.h "Split calls"): the first half of process_frame for up to max_group_frames frames -- features
+    // [n_frames][n_streams][42] and silence flags [n_frames][n_streams] out -- and the second half with the caller's band gains
+    // [n_frames][n_streams][22] in place of the network's (vad [n_frames][n_streams] optional).  `layout` describes the audio buffer of
+    // each half.  Device buffers, asynchronous; an analyze is followed by the synthesize of the same n_frames before any other call.
+    void analyze_device(const void *d_in, float *d_features, int32_t *d_silence, int n_frames, const nnn_pcm_layout &layout, void *hip_stream = nullptr)
+    {
+        check(nnn_batch_analyze_device(b_.get(), d_in, d_features, d_silence, n_frames, &layout, hip_stream));
+    }
+    void synthesize_device(const float *d_gains, const float *d_vad, void *d_out, int n_frames, const nnn_pcm_layout &layout, void *hip_stream = nullptr)
+    {
+        check(nnn_batch_synthesize_device(b_.get(), d_gains, d_vad, d_out, n_frames, &layout, hip_stream));
+    }
+    // the same with host buffers (staged in one piece, synchronous)
+    void analyze(const void *in, float *features, int32_t *silence, int n_frames, const nnn_pcm_layout &layout)
+    {
+        check(nnn_batch_analyze_host(b_.get(), in, features, silence, n_frames, &layout));
+    }
+    void synthesize(const float *gains, const float *vad, void *out, int n_frames, const nnn_pcm_layout &layout)
+    {
+        check(nnn_batch_synthesize_host(b_.get(), gains, vad, out, n_frames, &layout));
+    }
+    int pending_frames() const { return nnn_batch_pending_frames(b_.get()); }
     void synchronize() { check(nnn_batch_synchronize(b_.get())); }
     // true once a frame hand-off inside the pitch stage has failed (nnn_batch_fault): sticky until reset() / load_state(); for hosts
     // that synchronise their own HIP stream instead of calling synchronize()

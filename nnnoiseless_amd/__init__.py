@@ -311,6 +311,80 @@ class BatchDenoiser:
         self._lib.check(self._lib.L.nnn_batch_process_pcm_device(self._h, d_in, d_out, d_vad, n_frames, C.byref(L), hip_stream))
         self.frames_done += n_frames
 
+    # ---- split calls: features out, the caller's gains in (include/nnn_batch.h "Split calls") ----
+    def _pcm_shape(self, what, x, fmt, channels):
+        """The audio conventions of process (fmt None: float32 [n_streams, n_frames, 480]) and process_pcm (packed
+        [n_streams / channels, n_frames * 480, channels]): (array, format, channels, frames, group stride)."""
+        if fmt is None:
+            x = _ffi.as_f32(x)
+            if x.ndim != 3 or x.shape[0] != self.n_streams or x.shape[2] != FRAME_SIZE:
+                raise ValueError(f"{what} needs audio of shape [{self.n_streams}, n_frames, {FRAME_SIZE}], got {x.shape}")
+            return x, _ffi.PCM_F32, 1, x.shape[1], x.shape[1] * FRAME_SIZE
+        x = np.ascontiguousarray(x, dtype=_ffi.PCM_DTYPE[fmt])
+        if x.ndim != 3 or x.shape[2] != channels or x.shape[0] * channels != self.n_streams or x.shape[1] % FRAME_SIZE:
+            raise ValueError(f"{what} needs audio of shape [n_streams / channels, n_frames * {FRAME_SIZE}, channels], got {x.shape}")
+        return x, fmt, channels, x.shape[1] // FRAME_SIZE, x.shape[1] * channels
+
+    def analyze(self, x, fmt=None, channels=1, features=None, silence=None):
+        """The first half of process_frame for up to max_group_frames() frames: x as process takes it (fmt None) or as process_pcm does
+        (fmt, channels) -> (features float32 [n_frames, n_streams, 42], silence int32 [n_frames, n_streams]).  The frames are pending
+        until synthesize() is given their gains.  `features` / `silence`, when handed in, are written in place: held streams' rows stay."""
+        x, fmt, channels, T, gstride = self._pcm_shape("analyze", x, fmt, channels)
+        S = self.n_streams
+        features = np.zeros((T, S, NB_FEATURES), np.float32) if features is None else features
+        silence = np.zeros((T, S), np.int32) if silence is None else silence
+        for a, shp, dt, name in ((features, (T, S, NB_FEATURES), np.float32, "features"), (silence, (T, S), np.int32, "silence")):
+            if not (isinstance(a, np.ndarray) and a.shape == shp and a.dtype == dt and a.flags.c_contiguous and a.flags.writeable):
+                raise ValueError(f"analyze: `{name}` must be a writable C-contiguous {np.dtype(dt).name} array of shape {list(shp)}")
+        L = _ffi.PcmLayout(fmt, channels, 0, 0, gstride, FRAME_SIZE * channels)
+        self._lib.check(self._lib.L.nnn_batch_analyze_host(self._h, _ffi.ptr(x), _ffi.ptr(features), _ffi.ptr(silence), T, C.byref(L)))
+        return features, silence
+
+    def synthesize(self, gains, vad=None, fmt=None, channels=1, discard_first=False, out=None):
+        """The second half for the pending frames: gains float32 [n_frames, n_streams, 22] (vad [n_frames, n_streams], optional: the
+        network's VAD, kept for tap("vad")) -> audio in the convention analyze read it in (process's for fmt None, process_pcm's
+        otherwise, discard_first as there).  `out`, when handed in, is written in place: what held streams own in it stays."""
+        gains = _ffi.as_f32(gains)
+        S = self.n_streams
+        if gains.ndim != 3 or gains.shape[1:] != (S, NB_BANDS):
+            raise ValueError(f"synthesize needs gains of shape [n_frames, {S}, {NB_BANDS}], got {gains.shape}")
+        T = gains.shape[0]
+        if vad is not None:
+            vad = _ffi.as_f32(vad)
+            if vad.shape != (T, S):
+                raise ValueError(f"synthesize: `vad` must have shape [{T}, {S}], got {vad.shape}")
+        if fmt is None:
+            fmt_, channels, shape, dt = _ffi.PCM_F32, 1, (S, T, FRAME_SIZE), np.float32
+        else:
+            if channels < 1 or S % channels:
+                raise ValueError("n_streams must be a multiple of channels")
+            fmt_, shape, dt = fmt, (S // channels, T * FRAME_SIZE, channels), _ffi.PCM_DTYPE[fmt]
+        out = np.zeros(shape, dt) if out is None else out
+        if not (isinstance(out, np.ndarray) and out.shape == shape and out.dtype == dt and out.flags.c_contiguous and out.flags.writeable):
+            raise ValueError(f"synthesize: `out` must be a writable C-contiguous {np.dtype(dt).name} array of shape {list(shape)}")
+        L = _ffi.PcmLayout(fmt_, channels, int(bool(discard_first)), 0, T * FRAME_SIZE * channels, FRAME_SIZE * channels)
+        fresh = self.frames_done == 0
+        self._lib.check(self._lib.L.nnn_batch_synthesize_host(self._h, _ffi.ptr(gains), _ffi.ptr(vad), _ffi.ptr(out), T, C.byref(L)))
+        self.frames_done += T
+        if fmt is None:
+            return out
+        return out[:, :(T - 1 if (discard_first and fresh) else T) * FRAME_SIZE]
+
+    def analyze_device(self, d_in, d_features, d_silence, n_frames, fmt, channels, group_stride, frame_stride, hip_stream=0):
+        """Raw device pointers (ints), strides in elements of the format; asynchronous on hip_stream (0 = the batch's own stream)."""
+        L = _ffi.PcmLayout(fmt, channels, 0, 0, group_stride, frame_stride)
+        self._lib.check(self._lib.L.nnn_batch_analyze_device(self._h, d_in, d_features, d_silence, n_frames, C.byref(L), hip_stream))
+
+    def synthesize_device(self, d_gains, d_vad, d_out, n_frames, fmt, channels, group_stride, frame_stride, discard_first=False, hip_stream=0):
+        """Raw device pointers (d_vad may be None); asynchronous."""
+        L = _ffi.PcmLayout(fmt, channels, int(bool(discard_first)), 0, group_stride, frame_stride)
+        self._lib.check(self._lib.L.nnn_batch_synthesize_device(self._h, d_gains, d_vad, d_out, n_frames, C.byref(L), hip_stream))
+        self.frames_done += n_frames
+
+    def pending_frames(self):
+        """Frames analysed and not yet synthesised (0 = none)."""
+        return int(self._lib.L.nnn_batch_pending_frames(self._h))
+
     def synchronize(self):
         self._lib.check(self._lib.L.nnn_batch_synchronize(self._h))
 

@@ -23,6 +23,7 @@ BATCH_SYMBOLS = [
     "nnn_batch_create_opts", "nnn_batch_max_group_frames", "nnn_batch_device_bytes", "nnn_batch_set_back_end", "nnn_device_local_cpulist",
     "nnn_batch_reset_streams", "nnn_batch_export_streams", "nnn_batch_import_streams", "nnn_batch_export_streams_device",
     "nnn_batch_import_streams_device", "nnn_batch_hold_streams", "nnn_batch_resume_streams", "nnn_batch_num_held", "nnn_batch_held_mask",
+    "nnn_batch_analyze_device", "nnn_batch_synthesize_device", "nnn_batch_analyze_host", "nnn_batch_synthesize_host", "nnn_batch_pending_frames",
 ]
 TRAIN_SYMBOLS = [
     "nnn_train_create", "nnn_train_destroy", "nnn_train_reset", "nnn_train_process_device", "nnn_train_process_host",
@@ -157,6 +158,13 @@ class Library:
             L.nnn_batch_resume_streams.argtypes = [vp, ip, i32]
             L.nnn_batch_num_held.argtypes = [vp]
             L.nnn_batch_held_mask.argtypes = [vp, vp, sz]
+        if hasattr(L, "nnn_batch_analyze_device"):
+            lp = C.POINTER(PcmLayout)
+            L.nnn_batch_analyze_device.argtypes = [vp, vp, vp, vp, i32, lp, vp]
+            L.nnn_batch_synthesize_device.argtypes = [vp, vp, vp, vp, i32, lp, vp]
+            L.nnn_batch_analyze_host.argtypes = [vp, vp, vp, vp, i32, lp]
+            L.nnn_batch_synthesize_host.argtypes = [vp, vp, vp, vp, i32, lp]
+            L.nnn_batch_pending_frames.argtypes = [vp]
         if hasattr(L, "nnn_node_hold_streams"):
             ip = C.POINTER(i32)
             L.nnn_node_hold_streams.argtypes = [vp, ip, i32]

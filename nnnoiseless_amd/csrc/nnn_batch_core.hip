@@ -85,6 +85,15 @@ static const char *kKernelNames[K_COUNT] = {"k_hp", "k_lpc", "k_pitch", "k_fft_x
 // state from frame to frame and loop over the group's frames inside the launch; fft_xp covers all frames of the group
 // side by side (block index = frame * blocks_per_frame + block).
 enum Stage { ST_HP, ST_PITCH, ST_FFT, ST_RNN, ST_SYN, ST_COUNT };
+// The two launches only the split calls make (launch_stage; no events, no schedule nodes: a split call is one group in order on one stream):
+// ST_FEAT ends nnn_batch_analyze_* (k_features, then the rows out), ST_GAINS begins nnn_batch_synthesize_* (the caller's gains in).
+enum SplitStage { ST_FEAT = ST_COUNT, ST_GAINS };
+struct SplitIo {                   // the caller's row buffers of a split call (device memory)
+    float *features = nullptr;     // [n_frames][n_streams][42]
+    int *silence = nullptr;        // [n_frames][n_streams]
+    const float *gains = nullptr;  // [n_frames][n_streams][22]
+    const float *vad = nullptr;    // [n_frames][n_streams], may be null
+};
 constexpr int NSTREAMS = 5;    // internal streams of a pipelined call
 constexpr int EVR = 16;        // event ring: groups of one call that may still be referred to
 enum SchedMode { SCHED_SEQ = 0, SCHED_LANES = 1, SCHED_STAGES = 2 };
@@ -273,7 +282,19 @@ struct nnn_batch {
     unsigned long long *live = nullptr;   // device: Buffers::live of every scratch set's argument block
     std::vector<uint8_t> held;         // the host's copy of the mask, for checking arguments and for the host-buffer calls' copies back
     int n_held = 0;
+    // split calls (nnn_batch_analyze_* / nnn_batch_synthesize_*): frames analysed and not yet synthesised, the
+    // scratch sets they lie in and the ring slot of the first one
+    int pending = 0, pending_set0 = 0, pending_slot = 0;
+    GrowBuf<float> split_stage;        // the host variants' rows on the device: features | silence, or gains | vad (capacity in frames)
 };
+
+// While frames are pending every call that reads or moves per-stream state is refused, changing nothing (include/nnn_batch.h).
+static int refuse_pending(const nnn_batch *h, const char *what)
+{
+    if (!h || !h->pending) return 0;
+    return fail("%s refused: %d frames are pending (analysed by nnn_batch_analyze_* and not yet synthesised); "
+                "nnn_batch_synthesize_* of the same n_frames comes first (nnn_batch_reset drops them)", what, h->pending);
+}
 
 // A pitch workgroup that never saw its predecessor's hand-off flag went on with a stale pitch: the streams' state is invalid from
 // that frame on.  Sticky: every later call and nnn_batch_synchronize report it until nnn_batch_reset / nnn_batch_load_state.

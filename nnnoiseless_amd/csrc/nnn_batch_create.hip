@@ -73,6 +73,7 @@ extern "C" void nnn_batch_destroy(nnn_batch *h)
     if (h->copy_out) hipStreamDestroy(h->copy_out);
     h->stage.release();
     h->stage_vad.release();
+    h->split_stage.release();
     h->zc_host.release();
     if (h->ss_dims) hipFree(h->ss_dims);
     if (h->ss_flag) hipFree(h->ss_flag);
@@ -432,5 +433,6 @@ extern "C" int nnn_batch_reset(nnn_batch *h)
     h->group_count = 0;
     h->last_set = 0;
     h->prev_pipe = false;
+    h->pending = 0;   // (frames analysed and never synthesised are dropped with the rest)
     return 0;
 }

@@ -223,6 +223,7 @@ extern "C" int nnn_batch_process_host(nnn_batch *h, const float *in, float *out,
                                       size_t stream_stride, size_t frame_stride)
 {
     if (!h) return fail("null batch");
+    if (int rc = refuse_pending(h, "nnn_batch_process_host")) return rc;
     if (n_frames <= 0) return 0;
     if (!in || !out) return fail("null buffer");
     if (n_frames > 1 && frame_stride < (size_t)FRAME) return fail("frame_stride smaller than one frame");
@@ -234,6 +235,7 @@ extern "C" int nnn_batch_process_pcm_host(nnn_batch *h, const void *in, void *ou
                                           const nnn_pcm_layout *L)
 {
     if (!h) return fail("null batch");
+    if (int rc = refuse_pending(h, "nnn_batch_process_pcm_host")) return rc;
     if (n_frames <= 0) return 0;
     if (!in || !out) return fail("null buffer");
     if (int rc = check_layout(h, L)) return rc;

@@ -110,7 +110,8 @@ static const void *const kBigLdsKernels[] = {
 // stage `s` of the group planned in p, in scratch sets set0 .. set0 + p.g - 1, parameters at sp0[0..g), on stream `st`.
 // plain_out: the parameter table sp0 points into was filled for f32 mono audio (k_synth's plain-format instantiation ignores the table's
 // fmt / channels, so the caller states the format of the very call that fills the table, not a field of the batch)
-static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, const StepParams *sp0, hipStream_t st, bool prof, bool plain_out, const StepParams *call = nullptr, int fill = 0)
+static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, const StepParams *sp0, hipStream_t st, bool prof, bool plain_out, const StepParams *call = nullptr, int fill = 0,
+                         const SplitIo *io = nullptr)
 {
     const int g = p.g;
     if (g <= 0) return;   // (never a launch with an empty grid)
@@ -173,6 +174,14 @@ static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, cons
         if (p.back == BACK_FUSED) break;
         if (plain_out) L.go(K_SYNTH, k_synth<true>, dim3(Sp / FFT_SPB), dim3(64 * FFT_SPB), 0, b, sp0, g);
         else L.go(K_SYNTH, k_synth<false>, dim3(Sp / FFT_SPB), dim3(64 * FFT_SPB), 0, b, sp0, g);
+        break;
+    // the split calls' boundary launches (io: the caller's rows).  Not in the timing table: untimed, like the training rows' k_features.
+    case ST_FEAT:
+        hipLaunchKernelGGL(k_features, dim3(NT), dim3(64 * FEAT_WAVES), 0, st, b, g);
+        hipLaunchKernelGGL(k_features_out, dim3(NT * ug), dim3(FOUT_T), 0, st, b, io->features, io->silence, g);
+        break;
+    case ST_GAINS:
+        hipLaunchKernelGGL(k_gains_in, dim3(NT), dim3(GIN_T), 0, st, b, io->gains, io->vad, g);
         break;
     }
 }
@@ -474,6 +483,7 @@ extern "C" int nnn_batch_process_device(nnn_batch *h, const float *d_in, float *
                                         size_t stream_stride, size_t frame_stride, void *hip_stream)
 {
     if (!h) return fail("null batch");
+    if (int rc = refuse_pending(h, "nnn_batch_process_device")) return rc;
     if (n_frames <= 0) return 0;
     if (!d_in || !d_out) return fail("null buffer");
     if (n_frames > 1 && frame_stride < (size_t)FRAME) return fail("frame_stride smaller than one frame");
@@ -485,6 +495,7 @@ extern "C" int nnn_batch_process_pcm_device(nnn_batch *h, const void *d_in, void
                                             const nnn_pcm_layout *L, void *hip_stream)
 {
     if (!h) return fail("null batch");
+    if (int rc = refuse_pending(h, "nnn_batch_process_pcm_device")) return rc;
     if (n_frames <= 0) return 0;
     if (!d_in || !d_out) return fail("null buffer");
     if (int rc = check_layout(h, L)) return rc;

@@ -18,6 +18,7 @@ extern "C" int nnn_batch_save_state(nnn_batch *h, void *host_dst, size_t dst_byt
 {
     NNN_RT_LOCK;
     if (!h || !host_dst) return fail("null argument");
+    if (int rc = refuse_pending(h, "nnn_batch_save_state")) return rc;
     const size_t need = nnn_batch_state_bytes(h);
     if (dst_bytes < need) return fail("state buffer too small: %zu bytes needed", need);
     if (h->n_held) return fail("nnn_batch_save_state refused: %d streams are held (nnn_batch_hold_streams) and the raw state image has no place for their parked records; resume or export them first", h->n_held);
@@ -37,6 +38,7 @@ extern "C" int nnn_batch_load_state(nnn_batch *h, const void *host_src, size_t s
 {
     NNN_RT_LOCK;
     if (!h || !host_src) return fail("null argument");
+    if (int rc = refuse_pending(h, "nnn_batch_load_state")) return rc;
     const size_t need = nnn_batch_state_bytes(h);
     SnapHeader hd;
     if (src_bytes < sizeof(hd)) return fail("not a state snapshot");
@@ -62,6 +64,7 @@ extern "C" nnn_batch *nnn_batch_clone(nnn_batch *h)
 {
     NNN_RT_LOCK;
     if (!h) { fail("null batch"); return nullptr; }
+    if (refuse_pending(h, "nnn_batch_clone")) return nullptr;
     if (quiesce(h)) return nullptr;
     std::vector<const RNNModel *> mp;
     for (const RNNModel &m : h->models) mp.push_back(&m);

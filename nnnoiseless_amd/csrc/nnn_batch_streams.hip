@@ -30,6 +30,8 @@ enum SsOp { SS_RESET = 0, SS_EXPORT = 1, SS_IMPORT = 2, SS_HOLD = 3, SS_RESUME =
 int nnn_batch_check_streams(const nnn_batch *h, int op, const int *streams, int n, const void *host_rec, size_t bytes, bool need_buf)
 {
     if (!h) return fail("null batch");
+    static const char *const kOpNames[] = {"nnn_batch_reset_streams", "nnn_batch_export_streams", "nnn_batch_import_streams", "nnn_batch_hold_streams", "nnn_batch_resume_streams"};
+    if (int rc = refuse_pending(h, kOpNames[op])) return rc;
     if (n < 0) return fail("negative stream count");
     if (n > 0 && !streams) return fail("null stream list");
     if (op == SS_EXPORT && nnn_batch_fault(h)) return fail("export refused: the batch is faulted (nnn_batch_fault); its state is invalid");
