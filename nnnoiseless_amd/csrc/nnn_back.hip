@@ -34,102 +34,47 @@ constexpr int BK_GW = 48;        // per-stream gains handed to the synthesis: ra
 // The kernel is compiled for a SHAPE CLASS -- the layer sizes (input dense, vad / noise / denoise GRU neurons) as compile-time constants,
 // so that every LDS offset, row stride, k-step count and unit count is an immediate and every k-step loop unrolls; with the plan as
 // run-time values (k_rnn's way) a 16-wave kernel that also holds two spectra per wave runs out of scalar registers (500 scalar spills
-// into vector registers in the first build).  bk_make_plan restates nnn_model_pack's column plan and packing offsets (nnn_model.cpp)
-// for given sizes; the host compares it with the model's own plan field by field and takes the unfused kernels for any model outside
-// the compiled classes.  Activation kinds stay run-time values (the models of a class differ in them).
-constexpr int bk_pad(int v, int m) { return (v + m - 1) / m * m; }
-constexpr int bk_ks(int cols) { return (cols + 31) / 32; }
-constexpr GemmDesc bk_gd(int &at, int n, int ngates, int ksteps, int kbase)
-{
-    GemmDesc g{at, ksteps, kbase, ngates};
-    at += bk_pad(n, 16) / 16 * ngates * ksteps * 64;
-    return g;
-}
-constexpr LayerDesc bk_ld(GemmDesc in, GemmDesc rec, int n, int &bias_at, int nbias, int out_col)
-{
-    LayerDesc L{in, rec, n, bk_pad(n, 16) / 16, 0, bias_at, out_col};
-    bias_at += nbias;
-    return L;
-}
-constexpr RnnPlan bk_make_plan(int nd, int nv, int nn, int ndn)
-{
-    const int cN = 0, cV = bk_pad(nn, 8), cF = cV + bk_pad(nv, 8), cD = cF + 48, NF = 42;
-    int at = 0, bias = 0;
-    RnnPlan p{};
-    const GemmDesc none{0, 0, 0, 0};
-    const GemmDesc d_in = bk_gd(at, nd, 1, 2, cF);
-    p.dense = bk_ld(d_in, none, nd, bias, nd, cD);
-    const GemmDesc v_in = bk_gd(at, nv, 3, bk_ks(nd), cD), v_rec = bk_gd(at, nv, 3, bk_ks(nv), 0);
-    p.vad = bk_ld(v_in, v_rec, nv, bias, 3 * nv, cV);
-    const GemmDesc n_in = bk_gd(at, nn, 3, bk_ks(cD + nd - cV), cV), n_rec = bk_gd(at, nn, 3, bk_ks(nn), 0);
-    p.noise = bk_ld(n_in, n_rec, nn, bias, 3 * nn, cN);
-    const GemmDesc dn_in = bk_gd(at, ndn, 3, bk_ks(cF + NF), 0), dn_rec = bk_gd(at, ndn, 3, bk_ks(ndn), 0);
-    p.dn = bk_ld(dn_in, dn_rec, ndn, bias, 3 * ndn, 0);
-    const GemmDesc o_in = bk_gd(at, 22, 1, bk_ks(ndn), 0);
-    p.out = bk_ld(o_in, none, 22, bias, 22, 0);
-    p.vo_w = bias;
-    p.vo_b = bias + nv;
-    p.act_vo = 0;
-    p.cF = cF;
-    p.cV = cV;
-    int width = bk_pad(ndn, 8);
-    const GemmDesc all[5] = {d_in, v_in, n_in, dn_in, o_in};
-    for (int i = 0; i < 5; i++) width = width > all[i].kbase + 32 * all[i].ksteps ? width : all[i].kbase + 32 * all[i].ksteps;
-    p.in_w = bk_pad(width, 16) + 8;
-    const int widest = nv > nn ? (nv > ndn ? nv : ndn) : (nn > ndn ? nn : ndn);
-    p.rec_w = bk_pad(32 * bk_ks(widest), 16) + 8;
-    return p;
-}
-// everything of two plans but the activation kinds
-inline bool bk_same_shape(const RnnPlan &a, const RnnPlan &b)
-{
-    auto gd = [](const GemmDesc &x, const GemmDesc &y) { return x.wofs == y.wofs && x.ksteps == y.ksteps && x.kbase == y.kbase && x.ngates == y.ngates; };
-    auto ld = [&](const LayerDesc &x, const LayerDesc &y) {
-        return gd(x.in, y.in) && gd(x.rec, y.rec) && x.n == y.n && x.nb == y.nb && x.bias == y.bias && x.out_col == y.out_col;
-    };
-    return a.in_w == b.in_w && a.rec_w == b.rec_w && a.cF == b.cF && a.cV == b.cV && ld(a.dense, b.dense) && ld(a.vad, b.vad) && ld(a.noise, b.noise) &&
-           ld(a.dn, b.dn) && ld(a.out, b.out) && a.vo_w == b.vo_w && a.vo_b == b.vo_b;
-}
-// the built-in model's class (src/weights.rnn; GregorR's rnnoise-models share it): 24 / 24 / 48 / 96
-struct BkShapeBuiltin { static constexpr RnnPlan plan() { return bk_make_plan(24, 24, 48, 96); } };
+// into vector registers in the first build).  The class's plan is rnn_plan_for of its sizes (nnn_layout.h, BkShapeBuiltin) -- the function
+// the packer lays every model out by -- so a model is in the class exactly when its four layer sizes are the class's; the host takes the
+// unfused kernels for any other model.  Activation kinds stay run-time values (the models of a class differ in them).
 
 // byte offsets into the kernel's dynamic LDS
 struct BackLds {
     int tab, live, flag, vadl, gout, crs, dcw, cnw, FS, SPv, SPn, SPdn, tbl, U, IN, RS, ZB, Z, part, total;
     int sw_v, sw_n, sw_dn;
 };
-constexpr int bk_take(int &at, int bytes) { const int r = at; at += (bytes + 15) & ~15; return r; }
 constexpr BackLds back_lds(const RnnPlan &pl, bool fused)
 {
     BackLds o{};
-    o.sw_v = 32 * pl.vad.rec.ksteps + 8; o.sw_n = 32 * pl.noise.rec.ksteps + 8; o.sw_dn = 32 * pl.dn.rec.ksteps + 8;
+    o.sw_v = rnn_state_w(pl.vad); o.sw_n = rnn_state_w(pl.noise); o.sw_dn = rnn_state_w(pl.dn);
     int at = 0;
-    o.tab = bk_take(at, 256 * 4);
-    o.live = bk_take(at, BK_ROWS * 4);
-    o.flag = bk_take(at, BK_ROWS * 4);
-    o.vadl = bk_take(at, BK_ROWS * 4);
-    o.gout = bk_take(at, BK_ROWS * BK_GW * 4);
-    o.crs = bk_take(at, BK_ROWS * CEPS_MEM * NB * 4);
-    o.dcw = bk_take(at, BK_ROWS * BK_CW * 4);
-    o.cnw = bk_take(at, BK_ROWS * BK_CW * 4);
-    o.FS = bk_take(at, 3 * BK_ROWS * FS_W * 2);
-    o.SPv = bk_take(at, 3 * BK_ROWS * o.sw_v * 2);
-    o.SPn = bk_take(at, 3 * BK_ROWS * o.sw_n * 2);
-    o.SPdn = bk_take(at, 3 * BK_ROWS * o.sw_dn * 2);
-    o.tbl = fused ? bk_take(at, (int)sizeof(FftLds)) : at;
+    o.tab = lds_take(at, 256 * 4);
+    o.live = lds_take(at, BK_ROWS * 4);
+    o.flag = lds_take(at, BK_ROWS * 4);
+    o.vadl = lds_take(at, BK_ROWS * 4);
+    o.gout = lds_take(at, BK_ROWS * BK_GW * 4);
+    o.crs = lds_take(at, BK_ROWS * CEPS_MEM * NB * 4);
+    o.dcw = lds_take(at, BK_ROWS * BK_CW * 4);
+    o.cnw = lds_take(at, BK_ROWS * BK_CW * 4);
+    o.FS = lds_take(at, 3 * BK_ROWS * FS_W * 2);
+    o.SPv = lds_take(at, 3 * BK_ROWS * o.sw_v * 2);
+    o.SPn = lds_take(at, 3 * BK_ROWS * o.sw_n * 2);
+    o.SPdn = lds_take(at, 3 * BK_ROWS * o.sw_dn * 2);
+    o.tbl = fused ? lds_take(at, (int)sizeof(FftLds)) : at;
     o.U = at;
     // the RNN's per-frame operands ...
-    o.IN = bk_take(at, 3 * BK_ROWS * pl.in_w * 2);
-    o.RS = bk_take(at, 3 * BK_ROWS * pl.rec_w * 2);
-    o.ZB = bk_take(at, BK_ROWS * BK_ZW * 4);
+    o.IN = lds_take(at, 3 * BK_ROWS * pl.in_w * 2);
+    o.RS = lds_take(at, 3 * BK_ROWS * pl.rec_w * 2);
+    o.ZB = lds_take(at, BK_ROWS * BK_ZW * 4);
     const int end_rnn = at;
     // ... share their space with the transforms' buffers: neither outlives its stretch of the frame
     at = o.U;
-    o.Z = bk_take(at, fused ? BK_ROWS * NFFT_BUF * 8 : 0);
-    o.part = bk_take(at, fused ? BK_ROWS * 3 * 64 * 4 : 0);
+    o.Z = lds_take(at, fused ? BK_ROWS * NFFT_BUF * 8 : 0);
+    o.part = lds_take(at, fused ? BK_ROWS * 3 * 64 * 4 : 0);
     o.total = at > end_rnn ? at : end_rnn;
     return o;
 }
+static_assert(back_lds(BkShapeBuiltin::plan(), true).total == 147952 && back_lds(BkShapeBuiltin::plan(), false).total == 80576, "k_back's LDS for the built-in shape class");
 
 // ---- the feature stage of one frame for one stream on its own wave (ref: src/features.rs:170-219): ring update, the 7 pair distances
 //      the new cepstrum takes part in (lane = partner row), the 42 outputs (lane = output).  Same operations in the same order as
@@ -393,12 +338,8 @@ __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0,
     pl.dense.act = acts.dense; pl.vad.act = acts.vad; pl.noise.act = acts.noise; pl.dn.act = acts.dn; pl.out.act = acts.out; pl.act_vo = acts.vo;
     const int wave0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane0 = threadIdx.x & 63;
     int wave = wave0, lane = lane0;
-    constexpr int per = TILE / BK_ROWS;
-    int tile, sub;
-    xcd_tile_block((int)blockIdx.x, (tile0 & 7) ? 1 : (int)gridDim.x / per, per, tile, sub);
-    tile += tile0;                                 // tile0: first tile of this model's run
-    const int r0 = sub * BK_ROWS;                  // first row of the tile handled here
-    if (tile * TILE + r0 >= b.S) return;   // (a block whose streams are all padding -- the last tile of a batch that is not a multiple of 64 -- has nothing to do)
+    int tile, r0;                                  // r0: first row of the tile handled here
+    if (!rnn_block_rows(b, tile0, BK_ROWS, tile, r0)) return;
     if (HELD && !live_any(b, tile, r0, BK_ROWS)) return;   // (... or all held, nnn_batch_hold_streams: the rider blocks of these streams returned too, xt_rider)
     const int sl = r0 + wave0, s = tile * TILE + sl;   // this wave's stream: its row in the tile, its index in the batch
     const int s_out = (HELD && !live_stream(b, tile, sl)) ? b.S_pad : s;   // (a held stream writes no audio, VAD or frame log: a padding stream's index, see k_synth)
@@ -536,10 +477,8 @@ __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0,
         NNN_STAMP(b, 8);
         // noise GRU (ref: src/rnn.rs:361-366); beside its first phase, on a wave it leaves idle, the vad output
         bk_gru_phase_a(pl.noise, R, SPn, o.sw_n, Wq, fpar, wave, lane, W, H);
-        if (wave == BK_WAVES - 1 && lane < BK_ROWS) {   // 1 x nv, lane = stream (ref: src/rnn.rs:359)
-            float acc = fpar[pl.vo_b];
-            for (int k = 0; k < pl.vad.n; k++) acc = fmaf(fpar[pl.vo_w + k], load_split(IN, in_ps, lane * pl.in_w + pl.cV + k), acc);
-            const float v = live[lane] ? activate(pl.act_vo, acc * (1.0f / 256.0f), tab) : 0.0f;
+        if (wave == BK_WAVES - 1 && lane < BK_ROWS) {
+            const float v = rnn_vad_out(pl, fpar, IN, in_ps, pl.in_w, pl.cV, lane, live, tab);
             vadl[lane] = v;
             NNN_TIF(b, vad, 1, f, tile, r0 + lane)[0] = v;
         }
@@ -553,7 +492,8 @@ __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0,
         bk_gru_phase_b(pl.dn, R, SPdn, o.sw_dn, Wq, lane, W, H);
         BK_EDGE(bk_dense_load(pl.out, Wq, fpar, wave, lane, W));
         NNN_STAMP(b, 10);
-        // gains (ref: src/rnn.rs:378) and smoothing g = max(g, 0.6 lastg) (ref: src/denoise.rs:106-109)
+        // gains (ref: src/rnn.rs:378) and smoothing g = max(g, 0.6 lastg) (ref: src/denoise.rs:106-109), as rnn_gain_out with the prefetched
+        // lastg; both also to `gout` for the synthesis
         bk_dense(pl.out, R, Wq, fpar, wave, lane, W, [&](int lrow, int band, float v, int q) {
             const int row = r0 + lrow;
             const bool lv = live[lrow] != 0;
@@ -586,17 +526,9 @@ __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0,
         NNN_STAMP(b, 12);
     }
     // ---- states back to HBM
-    {
-        auto save_state = [&](const LayerDesc &L, float *state, const unsigned short *SP, int sw) {
-            for (int e = (int)threadIdx.x; e < BK_ROWS * L.n; e += BK_T) {
-                const int row = e / L.n, col = e - row * L.n;
-                state[e] = load_split(SP, BK_ROWS * sw, row * sw + col);
-            }
-        };
-        save_state(pl.vad, sv, SPv, o.sw_v);
-        save_state(pl.noise, sn, SPn, o.sw_n);
-        save_state(pl.dn, sdn, SPdn, o.sw_dn);
-    }
+    gru_state_io<BK_T>(pl.vad, BK_ROWS, sv, SPv, o.sw_v, false);
+    gru_state_io<BK_T>(pl.noise, BK_ROWS, sn, SPn, o.sw_n, false);
+    gru_state_io<BK_T>(pl.dn, BK_ROWS, sdn, SPdn, o.sw_dn, false);
     if (lane0 == 0) NNN_TI(b.mem_id, 1, tile, sl)[0] = mem_id;
     NNN_STAMP(b, 13);
 }

@@ -1,6 +1,6 @@
 // nnn_batch_create.hip -- creation (decide, then act: plan_model_group, then one function per step), destruction, the small accessors,
 // synchronize and reset.
-// Needs nnn_batch_core.hip, hold_release_all of nnn_batch_streams.hip and kBigLdsKernels of nnn_batch_launch.hip.
+// Needs nnn_batch_core.hip, hold_release_all of nnn_batch_streams.hip and big_lds_kernels of nnn_batch_launch.hip.
 #pragma once
 
 // Tables.  Window and DCT follow the reference exactly (f64 math, f32 storage; src/lib.rs:107-127);
@@ -105,19 +105,21 @@ static nnn_batch::ModelGroup plan_model_group(const RnnPlan &pl, int ntiles, con
     // rows per block: the most that fit the LDS; fewer (more, shorter blocks) while the launch cannot fill the GPU
     G.rows = 0;
     for (int rows = 32; rows >= 16 && !G.rows; rows /= 2)   // (64 rows never fit: the states stay in LDS for a whole group)
-        if (rnn_lds_bytes(G.plan, rows) <= kLdsMax) G.rows = rows;
+        if ((size_t)rnn_lds(G.plan, rows).total <= kLdsMax) G.rows = rows;
     if (!G.rows) return G;
     while (G.rows > 16 && G.ntiles * (TILE / G.rows) < RNN_SMALL_BATCH_BLOCKS) G.rows /= 2;
-    if (paths.rnn_rows && rnn_lds_bytes(G.plan, paths.rnn_rows) <= kLdsMax) G.rows = paths.rnn_rows;
-    G.rnn_lds = rnn_lds_bytes(G.plan, G.rows);
+    if (paths.rnn_rows && (size_t)rnn_lds(G.plan, paths.rnn_rows).total <= kLdsMax) G.rows = paths.rnn_rows;
+    G.rnn_lds = (size_t)rnn_lds(G.plan, G.rows).total;
     // models of the built-in shape class run the layer-pipelined kernel (its fixed wave roles cover 2 / 2 / 3 / 6 neuron
     // blocks in the input dense / vad / noise / denoise layers)
     G.wp = wf_plan_of(G.plan);   // (strides of its per-layer matrices)
-    G.wf_lds = rnn_wf_lds_bytes(G.wp);
+    G.wf_lds = (size_t)wf_lds(G.wp).total;
     // the fused back end / its RNN stretch alone: layers of up to 8 neuron blocks (two units per wave) whose operands fit the LDS
-    // (compiled for the built-in model's shape class, nnn_back.hip; any other model takes the unfused kernels)
+    // (compiled for the built-in model's shape class; any other model takes the unfused kernels).  The packer laid the model out by
+    // rnn_plan_for of its four layer sizes, the kernels of the class read by rnn_plan_for of the class's: the same sizes, the same format
     {
-        const bool shape_ok = bk_same_shape(G.plan, BkShapeBuiltin::plan());
+        constexpr RnnPlan cls = BkShapeBuiltin::plan();
+        const bool shape_ok = pl.dense.n == cls.dense.n && pl.vad.n == cls.vad.n && pl.noise.n == cls.noise.n && pl.dn.n == cls.dn.n;
         G.shape_builtin = shape_ok;
         const size_t fb = (size_t)back_lds(G.plan, true).total, rb = (size_t)back_lds(G.plan, false).total;
         G.back_lds = shape_ok && fb <= kLdsMax ? fb : 0;
@@ -316,7 +318,7 @@ static int create_scratch_sets(nnn_batch *h)
 // the RNN kernels' dynamic LDS limit is a per-device function attribute: raise it to the hardware's 160 KB once
 static int raise_lds_limits()
 {
-    for (const void *k : kBigLdsKernels) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+    for (const void *k : big_lds_kernels()) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
     return 0;
 }
 

@@ -93,19 +93,26 @@ static void plan_group(const nnn_batch *h, int g, GroupPlan &p)
     }
 }
 
-// The kernels launched with more dynamic LDS than a function may have by default: creation raises each one's limit to the hardware's
-// 160 KB (raise_lds_limits).  Every k_rnn, k_rnn_wf and k_back instantiation of launch_stage below is listed here.
-static const void *const kBigLdsKernels[] = {
-    (const void *)k_rnn,
-    (const void *)k_rnn_wf<WfShapeAny>,
-    (const void *)k_rnn_wf<BkShapeBuiltin>,
-    (const void *)k_back<true, BkShapeBuiltin>,
-    (const void *)k_back<false, BkShapeBuiltin>,
-    (const void *)k_back<true, BkShapeBuiltin, true>,
-    (const void *)k_back<true, BkShapeBuiltin, false, true>,
-    (const void *)k_back<false, BkShapeBuiltin, false, true>,
-    (const void *)k_back<true, BkShapeBuiltin, true, true>,
-};
+// The kernels launched with more dynamic LDS than a function may have by default -- every k_rnn, k_rnn_wf and k_back instantiation.
+// launch_stage takes them from these tables and nowhere else, and creation raises the limit of every kernel in them to the hardware's
+// 160 KB (raise_lds_limits): an instantiation cannot be launched without having had its limit raised.
+using RnnWfKernel = decltype(&k_rnn_wf<WfShapeAny>);
+using BackKernel = decltype(&k_back<true, BkShapeBuiltin>);
+static const auto kRnnKernel = &k_rnn;
+static const RnnWfKernel kRnnWfKernels[2] = {k_rnn_wf<WfShapeAny>, k_rnn_wf<BkShapeBuiltin>};   // [the model is of the built-in shape class]
+static const BackKernel kBackFused[2][2] = {   // [X rides in k_pitch][some stream held]
+    {k_back<true, BkShapeBuiltin, false, false>, k_back<true, BkShapeBuiltin, false, true>},
+    {k_back<true, BkShapeBuiltin, true, false>, k_back<true, BkShapeBuiltin, true, true>}};
+static const BackKernel kBackRnnAlone[2] = {k_back<false, BkShapeBuiltin, false, false>, k_back<false, BkShapeBuiltin, false, true>};   // [some stream held]
+static std::vector<const void *> big_lds_kernels()
+{
+    std::vector<const void *> v{(const void *)kRnnKernel};
+    for (RnnWfKernel k : kRnnWfKernels) v.push_back((const void *)k);
+    for (const auto &by_held : kBackFused)
+        for (BackKernel k : by_held) v.push_back((const void *)k);
+    for (BackKernel k : kBackRnnAlone) v.push_back((const void *)k);
+    return v;
+}
 
 // stage `s` of the group planned in p, in scratch sets set0 .. set0 + p.g - 1, parameters at sp0[0..g), on stream `st`.
 // plain_out: the parameter table sp0 points into was filled for f32 mono audio (k_synth's plain-format instantiation ignores the table's
@@ -143,12 +150,8 @@ static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, cons
     }
     case ST_FFT:
         if (p.back == BACK_FUSED) {   // the fused back end takes the place of this stage and the two behind it: one launch per resident model
-            for (const nnn_batch::ModelGroup &G : h->groups) {
-                if (p.riders)   // (its X transform done by k_pitch's rider blocks, see xt_rider)
-                    L.go(K_BACK, p.held ? k_back<true, BkShapeBuiltin, true, true> : k_back<true, BkShapeBuiltin, true, false>, dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.back_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
-                else
-                    L.go(K_BACK, p.held ? k_back<true, BkShapeBuiltin, false, true> : k_back<true, BkShapeBuiltin, false, false>, dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.back_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
-            }
+            for (const nnn_batch::ModelGroup &G : h->groups)   // (riders: its X transform done by k_pitch's rider blocks, see xt_rider)
+                L.go(K_BACK, kBackFused[p.riders][p.held], dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.back_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
             break;
         }
         L.go(K_FFT_XP, k_fft_xp, dim3(Sp * ug / FFT_SPB), dim3(64 * FFT_SPB), 0, b, sp0, g);
@@ -158,15 +161,12 @@ static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, cons
         for (size_t i = 0; i < h->groups.size(); i++) {   // one launch per resident model (a run of whole tiles)
             const nnn_batch::ModelGroup &G = h->groups[i];
             if (p.rnn[i] == RK_BACK)
-                L.go(K_RNN, p.held ? k_back<false, BkShapeBuiltin, false, true> : k_back<false, BkShapeBuiltin, false, false>, dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.rnn16_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
-            else if (p.rnn[i] == RK_WF_BUILTIN)
-                L.go(K_RNN, k_rnn_wf<BkShapeBuiltin>, dim3((unsigned)(G.ntiles * (TILE / WF_ROWS))), dim3(64 * WF_WAVES), G.wf_lds, b, G.plan, G.wp,
-                     G.wq, G.fpar, G.tile0, g);
-            else if (p.rnn[i] == RK_WF_ANY)
-                L.go(K_RNN, k_rnn_wf<WfShapeAny>, dim3((unsigned)(G.ntiles * (TILE / WF_ROWS))), dim3(64 * WF_WAVES), G.wf_lds, b, G.plan, G.wp,
+                L.go(K_RNN, kBackRnnAlone[p.held], dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.rnn16_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
+            else if (p.rnn[i] == RK_WF_BUILTIN || p.rnn[i] == RK_WF_ANY)
+                L.go(K_RNN, kRnnWfKernels[p.rnn[i] == RK_WF_BUILTIN], dim3((unsigned)(G.ntiles * (TILE / WF_ROWS))), dim3(64 * WF_WAVES), G.wf_lds, b, G.plan, G.wp,
                      G.wq, G.fpar, G.tile0, g);
             else
-                L.go(K_RNN, k_rnn, dim3((unsigned)(G.ntiles * (TILE / G.rows))), dim3(64 * RNN_WAVES), G.rnn_lds, b, G.plan, G.wq, G.fpar,
+                L.go(K_RNN, kRnnKernel, dim3((unsigned)(G.ntiles * (TILE / G.rows))), dim3(64 * RNN_WAVES), G.rnn_lds, b, G.plan, G.wq, G.fpar,
                      G.tile0, G.rows, g);
         }
         break;

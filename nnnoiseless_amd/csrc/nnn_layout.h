@@ -87,6 +87,64 @@ struct RnnPlan {
     int vo_w, vo_b, act_vo;   // vad output layer (1 x nv), f32 parameters
 };
 
+// The packed format of a model of the given layer sizes (input dense, vad / noise / denoise GRU neurons): the LDS column plan, every GEMM's
+// k-steps and fragment offset, every bias offset -- all of an RnnPlan but the six activation kinds.  The one statement of the format:
+// nnn_model_pack (nnn_model.cpp) lays weights and biases out to it, the kernels compiled for a shape class (BkShapeBuiltin) read them by it.
+constexpr RnnPlan rnn_plan_for(int nd, int nv, int nn, int ndn)
+{
+    auto pad = [](int v, int m) { return (v + m - 1) / m * m; };
+    auto ks = [](int cols) { return (cols + 31) / 32; };
+    // LDS columns of the input matrix: [ noise state | vad state | features (48) | dense out ]
+    const int cN = 0, cV = pad(nn, 8), cF = cV + pad(nv, 8), cD = cF + 48, NF = 42;
+    int at = 0, bias = 0;
+    auto gemm = [&](int n, int ngates, int ksteps, int kbase) {
+        const GemmDesc g{at, ksteps, kbase, ngates};
+        at += pad(n, 16) / 16 * ngates * ksteps * 64;
+        return g;
+    };
+    auto layer = [&](GemmDesc in, GemmDesc rec, int n, int nbias, int out_col) {
+        const LayerDesc L{in, rec, n, pad(n, 16) / 16, 0, bias, out_col};
+        bias += nbias;
+        return L;
+    };
+    const GemmDesc none{0, 0, 0, 0};
+    RnnPlan p{};
+    p.dense = layer(gemm(nd, 1, 2, cF), none, nd, nd, cD);                                   // features -> D             (ref: src/rnn.rs:353-355)
+    const GemmDesc v_in = gemm(nv, 3, ks(nd), cD);                                           // vad GRU: input D          (ref: src/rnn.rs:356-358)
+    p.vad = layer(v_in, gemm(nv, 3, ks(nv), 0), nv, 3 * nv, cV);
+    const GemmDesc n_in = gemm(nn, 3, ks(cD + nd - cV), cV);                                 // noise GRU: columns cV ..   (ref: src/rnn.rs:361-366)
+    p.noise = layer(n_in, gemm(nn, 3, ks(nn), 0), nn, 3 * nn, cN);
+    const GemmDesc dn_in = gemm(ndn, 3, ks(cF + NF), 0);                                     // denoise GRU: columns 0 .. (ref: src/rnn.rs:368-377)
+    p.dn = layer(dn_in, gemm(ndn, 3, ks(ndn), 0), ndn, 3 * ndn, 0);
+    p.out = layer(gemm(22, 1, ks(ndn), 0), none, 22, 22, 0);                                 // gains: denoise state -> 22 (ref: src/rnn.rs:378)
+    p.vo_w = bias;                                                                           // vad output, 1 x nv        (ref: src/rnn.rs:359)
+    p.vo_b = bias + nv;
+    p.cF = cF;
+    p.cV = cV;
+    int width = pad(ndn, 8);       // the input matrix holds the denoise state and every input operand's k range
+    const GemmDesc ins[5] = {p.dense.in, p.vad.in, p.noise.in, p.dn.in, p.out.in};
+    for (const GemmDesc &g : ins) width = width > g.kbase + 32 * g.ksteps ? width : g.kbase + 32 * g.ksteps;
+    p.in_w = pad(width, 16) + 8;   // row stride = 16 bytes (mod 32): 16-byte fragment reads of 16 rows spread over all banks
+    const int widest = nv > nn ? (nv > ndn ? nv : ndn) : (nn > ndn ? nn : ndn);
+    p.rec_w = pad(32 * ks(widest), 16) + 8;
+    return p;
+}
+// where the packed buffers of a plan end: uint4 of weights, floats of biases and the vad output layer
+constexpr int rnn_plan_wq_len(const RnnPlan &p) { return p.out.in.wofs + p.out.nb * p.out.in.ksteps * 64; }
+constexpr int rnn_plan_fpar_len(const RnnPlan &p) { return p.vo_b + 1; }
+// row stride (bf16 elements) of a GRU layer's state planes in LDS, in every RNN kernel
+__host__ __device__ constexpr int rnn_state_w(const LayerDesc &L) { return 32 * L.rec.ksteps + 8; }
+
+// the built-in model's shape class (src/weights.rnn; GregorR's rnnoise-models share it): 24 / 24 / 48 / 96.  The kernels compiled for it
+// (k_rnn_wf<BkShapeBuiltin>, k_back) take every stride, column and offset below as a constant.
+struct BkShapeBuiltin { static constexpr RnnPlan plan() { return rnn_plan_for(24, 24, 48, 96); } };
+namespace builtin_format {   // the format of the class, pinned: a change here is a change of what the kernels and every packed model mean
+constexpr RnnPlan p = BkShapeBuiltin::plan();
+static_assert(p.cV == 48 && p.cF == 72 && p.dense.out_col == 120 && p.in_w == 168 && p.rec_w == 104, "column plan of the built-in shape class");
+static_assert(rnn_plan_wq_len(p) == 12352 && p.vo_w == 550 && p.vo_b == 574 && rnn_plan_fpar_len(p) == 575, "packed sizes of the built-in shape class");
+static_assert(rnn_state_w(p.vad) == 40 && rnn_state_w(p.noise) == 72 && rnn_state_w(p.dn) == 104, "state widths of the built-in shape class");
+}   // namespace builtin_format
+
 struct Buffers {
     // ---- persistent per-stream state (src/denoise.rs:37-42, features.rs:18-46, pitch.rs:4-17, rnn.rs:65-70)
     int nslot;           // history ring slots of this batch (slots_for(gmax))

@@ -3,10 +3,9 @@
 // nnn_model_* entry points of include/nnn_batch.h.
 #include "nnn_model.h"
 
+#include <assert.h>
 #include <stdio.h>
 #include <string.h>
-
-#include <algorithm>
 
 #include "../../include/nnn_batch.h"
 
@@ -105,36 +104,28 @@ inline uint16_t bf16_of_int(int v)  // |v| <= 128: exact
     return (uint16_t)(u >> 16);
 }
 
-// Appends one GEMM operand in fragment order [neuron block][gate][k-step][lane][8]:
+// Appends GEMM operand `g` of the plan in fragment order [neuron block][gate][k-step][lane][8]:
 // element = W[colmap(k)][gate * n + neuron], k = kbase + 32 ks + 8 (lane >> 4) + e, neuron = 16 nb + (lane & 15).
 template <class ColMap>
-nnn::GemmDesc pack_gemm(std::vector<uint16_t> &wq, const int8_t *W, int row_stride, int n, int ngates, int ksteps, int kbase,
-                        ColMap colmap)
+void pack_gemm(std::vector<uint16_t> &wq, const nnn::GemmDesc &g, const int8_t *W, int row_stride, int n, ColMap colmap)
 {
-    nnn::GemmDesc g;
-    g.wofs = (int)(wq.size() / 8);
-    g.ksteps = ksteps;
-    g.kbase = kbase;
-    g.ngates = ngates;
+    assert(wq.size() == (size_t)g.wofs * 8);
     const int nb = pad_to(n, 16) / 16;
     for (int b = 0; b < nb; b++)
-        for (int gate = 0; gate < ngates; gate++)
-            for (int ks = 0; ks < ksteps; ks++)
+        for (int gate = 0; gate < g.ngates; gate++)
+            for (int ks = 0; ks < g.ksteps; ks++)
                 for (int lane = 0; lane < 64; lane++)
                     for (int e = 0; e < 8; e++) {
-                        int k = kbase + 32 * ks + 8 * (lane >> 4) + e, neuron = 16 * b + (lane & 15);
+                        int k = g.kbase + 32 * ks + 8 * (lane >> 4) + e, neuron = 16 * b + (lane & 15);
                         int row = colmap(k);
                         int v = (row >= 0 && neuron < n) ? W[(size_t)row * row_stride + gate * n + neuron] : 0;
                         wq.push_back(bf16_of_int(v));
                     }
-    return g;
 }
 }  // namespace
 
-size_t nnn_model_pack(const RNNModel &m, std::vector<uint16_t> &wq, std::vector<float> &fpar, nnn::RnnPlan &plan,
-                      nnn::ModelDims &md)
+void nnn_model_pack(const RNNModel &m, std::vector<uint16_t> &wq, std::vector<float> &fpar, nnn::RnnPlan &plan, nnn::ModelDims &md)
 {
-    using nnn::LayerDesc;
     wq.clear();
     fpar.clear();
     const int nd = m.input_dense.nb_neurons, nv = m.vad_gru.nb_neurons, nn = m.noise_gru.nb_neurons,
@@ -142,71 +133,48 @@ size_t nnn_model_pack(const RNNModel &m, std::vector<uint16_t> &wq, std::vector<
     md.nd = nd; md.nv = nv; md.nn = nn; md.ndn = ndn;
     md.act_d = m.input_dense.activation; md.act_v = m.vad_gru.activation; md.act_n = m.noise_gru.activation;
     md.act_dn = m.denoise_gru.activation; md.act_o = m.denoise_output.activation; md.act_vo = m.vad_output.activation;
+    // where everything goes is the plan's to say (nnn_layout.h); here the weights and biases are laid out to it
+    plan = nnn::rnn_plan_for(nd, nv, nn, ndn);
+    plan.dense.act = md.act_d; plan.vad.act = md.act_v; plan.noise.act = md.act_n; plan.dn.act = md.act_dn; plan.out.act = md.act_o;
+    plan.act_vo = md.act_vo;
     const int8_t *blob = m.blob.data();
-    // LDS columns of the input matrix: [ noise state | vad state | features (48) | dense out ]
-    const int cN = 0, cV = pad_to(nn, 8), cF = cV + pad_to(nv, 8), cD = cF + 48;
-    const int NF = 42;
-    auto ks_of = [](int cols) { return (cols + 31) / 32; };
-    auto fbias = [&](size_t ofs, int count) {
-        int at = (int)fpar.size();
+    const int cV = plan.cV, cF = plan.cF, cD = plan.dense.out_col, NF = 42;
+    auto fbias = [&](int at, size_t ofs, int count) {
+        assert(fpar.size() == (size_t)at);
         for (int i = 0; i < count; i++) fpar.push_back((float)blob[ofs + i]);
-        return at;
-    };
-    auto finish = [&](LayerDesc &L, int n, int act, int bias, int out_col) {
-        L.n = n;
-        L.nb = pad_to(n, 16) / 16;
-        L.act = act;
-        L.bias = bias;
-        L.out_col = out_col;
     };
     // input dense: features -> D                                  (ref: src/rnn.rs:353-355)
-    plan.dense.in = pack_gemm(wq, blob + m.input_dense.weights, nd, nd, 1, 2, cF,
-                              [&](int k) { return (k >= cF && k < cF + NF) ? k - cF : -1; });
-    plan.dense.rec = nnn::GemmDesc{0, 0, 0, 0};
-    finish(plan.dense, nd, m.input_dense.activation, fbias(m.input_dense.bias, nd), cD);
+    pack_gemm(wq, plan.dense.in, blob + m.input_dense.weights, nd, nd, [&](int k) { return (k >= cF && k < cF + NF) ? k - cF : -1; });
+    fbias(plan.dense.bias, m.input_dense.bias, nd);
     // vad GRU: input D                                             (ref: src/rnn.rs:356-358)
-    plan.vad.in = pack_gemm(wq, blob + m.vad_gru.weights, 3 * nv, nv, 3, ks_of(nd), cD,
-                            [&](int k) { return (k >= cD && k < cD + nd) ? k - cD : -1; });
-    plan.vad.rec = pack_gemm(wq, blob + m.vad_gru.rec, 3 * nv, nv, 3, ks_of(nv), 0, [&](int k) { return k < nv ? k : -1; });
-    finish(plan.vad, nv, m.vad_gru.activation, fbias(m.vad_gru.bias, 3 * nv), cV);
+    pack_gemm(wq, plan.vad.in, blob + m.vad_gru.weights, 3 * nv, nv, [&](int k) { return (k >= cD && k < cD + nd) ? k - cD : -1; });
+    pack_gemm(wq, plan.vad.rec, blob + m.vad_gru.rec, 3 * nv, nv, [&](int k) { return k < nv ? k : -1; });
+    fbias(plan.vad.bias, m.vad_gru.bias, 3 * nv);
     // noise GRU: reference input order [D | V | F]                 (ref: src/rnn.rs:361-366)
-    plan.noise.in = pack_gemm(wq, blob + m.noise_gru.weights, 3 * nn, nn, 3, ks_of(cD + nd - cV), cV, [&](int k) {
+    pack_gemm(wq, plan.noise.in, blob + m.noise_gru.weights, 3 * nn, nn, [&](int k) {
         if (k >= cV && k < cV + nv) return nd + (k - cV);
         if (k >= cF && k < cF + NF) return nd + nv + (k - cF);
         if (k >= cD && k < cD + nd) return k - cD;
         return -1;
     });
-    plan.noise.rec = pack_gemm(wq, blob + m.noise_gru.rec, 3 * nn, nn, 3, ks_of(nn), 0, [&](int k) { return k < nn ? k : -1; });
-    finish(plan.noise, nn, m.noise_gru.activation, fbias(m.noise_gru.bias, 3 * nn), cN);
+    pack_gemm(wq, plan.noise.rec, blob + m.noise_gru.rec, 3 * nn, nn, [&](int k) { return k < nn ? k : -1; });
+    fbias(plan.noise.bias, m.noise_gru.bias, 3 * nn);
     // denoise GRU: reference input order [V | N | F]               (ref: src/rnn.rs:368-377)
-    plan.dn.in = pack_gemm(wq, blob + m.denoise_gru.weights, 3 * ndn, ndn, 3, ks_of(cF + NF), 0, [&](int k) {
+    pack_gemm(wq, plan.dn.in, blob + m.denoise_gru.weights, 3 * ndn, ndn, [&](int k) {
         if (k < nn) return nv + k;
         if (k >= cV && k < cV + nv) return k - cV;
         if (k >= cF && k < cF + NF) return nv + nn + (k - cF);
         return -1;
     });
-    plan.dn.rec = pack_gemm(wq, blob + m.denoise_gru.rec, 3 * ndn, ndn, 3, ks_of(ndn), 0, [&](int k) { return k < ndn ? k : -1; });
-    finish(plan.dn, ndn, m.denoise_gru.activation, fbias(m.denoise_gru.bias, 3 * ndn), 0);
+    pack_gemm(wq, plan.dn.rec, blob + m.denoise_gru.rec, 3 * ndn, ndn, [&](int k) { return k < ndn ? k : -1; });
+    fbias(plan.dn.bias, m.denoise_gru.bias, 3 * ndn);
     // gains: denoise state (written to columns 0..ndn) -> 22       (ref: src/rnn.rs:378)
-    plan.out.in = pack_gemm(wq, blob + m.denoise_output.weights, 22, 22, 1, ks_of(ndn), 0, [&](int k) { return k < ndn ? k : -1; });
-    plan.out.rec = nnn::GemmDesc{0, 0, 0, 0};
-    finish(plan.out, 22, m.denoise_output.activation, fbias(m.denoise_output.bias, 22), 0);
+    pack_gemm(wq, plan.out.in, blob + m.denoise_output.weights, 22, 22, [&](int k) { return k < ndn ? k : -1; });
+    fbias(plan.out.bias, m.denoise_output.bias, 22);
     // vad output, 1 x nv, stays on the vector ALU                  (ref: src/rnn.rs:359)
-    plan.vo_w = fbias(m.vad_output.weights, nv);
-    plan.vo_b = fbias(m.vad_output.bias, 1);
-    plan.act_vo = m.vad_output.activation;
-    plan.cF = cF;
-    plan.cV = cV;
-    int width = 0;
-    auto need = [&](const nnn::GemmDesc &g) { width = std::max(width, g.kbase + 32 * g.ksteps); };
-    need(plan.dense.in); need(plan.vad.in); need(plan.noise.in); need(plan.dn.in); need(plan.out.in);
-    width = std::max(width, pad_to(ndn, 8));
-    plan.in_w = pad_to(width, 16) + 8;  // row stride = 16 bytes (mod 32): 16-byte fragment reads of 16 rows spread over all banks
-    plan.rec_w = pad_to(32 * ks_of(std::max(nv, std::max(nn, ndn))), 16) + 8;
-    (void)cN;
-    // dynamic LDS: tanh table (256 floats) + live flags (64 ints) + 3 planes of both matrices + the staged
-    // cepstral ring of the feature stage (8 x 22 rows of 64 floats) and its 28 pair distances
-    return 256 * 4 + 64 * 4 + (size_t)3 * 64 * (plan.in_w + plan.rec_w) * 2 + (size_t)(8 * 22 + 28) * 64 * 4;
+    fbias(plan.vo_w, m.vad_output.weights, nv);
+    fbias(plan.vo_b, m.vad_output.bias, 1);
+    assert(wq.size() == (size_t)nnn::rnn_plan_wq_len(plan) * 8 && fpar.size() == (size_t)nnn::rnn_plan_fpar_len(plan));
 }
 
 // ---- model entry points -------------------------------------------------------------------------

@@ -27,7 +27,8 @@ struct RNNModel {
 RNNModel *nnn_model_parse(const uint8_t *bytes, size_t len);
 const uint8_t *nnn_builtin_weights(size_t *len);
 
-// Pack the i8 weights for the MFMA RNN kernel: bf16 (exact: |w| <= 128) in B-fragment order, biases
-// and the vad output layer as f32, plus the LDS column plan.  Returns the dynamic LDS bytes the kernel needs.
-size_t nnn_model_pack(const RNNModel &m, std::vector<uint16_t> &wq, std::vector<float> &fpar, nnn::RnnPlan &plan,
+// Pack the i8 weights for the MFMA RNN kernels: bf16 (exact: |w| <= 128) in B-fragment order, biases
+// and the vad output layer as f32, laid out as rnn_plan_for (nnn_layout.h) says for the model's layer sizes;
+// `plan` is that plan with the model's activation kinds filled in.
+void nnn_model_pack(const RNNModel &m, std::vector<uint16_t> &wq, std::vector<float> &fpar, nnn::RnnPlan &plan,
                       nnn::ModelDims &md);

@@ -1,6 +1,8 @@
 #pragma once
-// nnn_rnn.hip -- K10, the network: activations, bf16 split planes, the MFMA GEMM pieces, the GRU and dense layers and k_rnn (layers one after
-// the other).  Not a translation unit: nnn_kernels.hip includes it between the feature stage and k_rnn_wf, which shares these pieces.
+// nnn_rnn.hip -- K10, the network: activations, bf16 split planes, the MFMA GEMM pieces, the layer pieces the three RNN kernels share (the
+// block prologue, state load and store, gain and VAD output), the GRU and dense layers and k_rnn (layers one after the other) with its
+// LDS layout.  Not a translation unit: nnn_kernels.hip includes it between the feature stage and k_rnn_wf; k_rnn_wf (nnn_rnn_wf.hip) and
+// k_back (nnn_back.hip) use these pieces.
 
 namespace nnn {
 
@@ -83,6 +85,7 @@ __device__ __forceinline__ void load_frags(Frags<NG, KS> &fr, const GemmDesc &g,
 
 // acc[G0 + g][mb] += A[16 (mb0 + mb) .. +15][kbase ..] * B(gate G0 + g), g < NG, mb < MB, over all k-steps and
 // the three activation planes.  Bnb points at this neuron block's fragments ([gate][k-step][lane]).
+// (k_back's bk_gemm / bk_frags_load stay a form of their own, as do the four feature stages: each a parallelisation chosen by measurement)
 template <int NG, int MB, int G0, int KS = KSMAX>
 __device__ __forceinline__ void gemm_acc(f32x4 (&acc)[3][2], const unsigned short *A, int plane_stride, int row_w, int mb0,
                                          const GemmDesc &g, const uint4 *__restrict__ Bnb, int lane, const Frags<NG, KS> &fr)
@@ -127,6 +130,60 @@ __device__ __forceinline__ void gemm_acc(f32x4 (&acc)[3][2], const unsigned shor
             for (int pl = 0; pl < GPL; pl++) cur[pl] = nxt[pl];
         }
     }
+}
+
+// ---- pieces the three RNN kernels share (k_rnn, k_rnn_wf, k_back): the same operations in the same order, so that they give the same bits
+
+// carving a kernel's dynamic LDS: the byte offset of the next `bytes` (whole 16-byte units)
+__host__ __device__ constexpr int lds_take(int &at, int bytes) { const int r = at; at += (bytes + 15) & ~15; return r; }
+
+// The block's tile and the first of its `rm` rows in it (blocks dealt over the XCDs by xcd_tile_block; tile0: first tile of this model's
+// run).  False: every stream of the block is padding -- the last tile of a batch that is not a multiple of 64 -- and it has nothing to do.
+__device__ __forceinline__ bool rnn_block_rows(const Buffers &b, int tile0, int rm, int &tile, int &r0)
+{
+    const int per = TILE / rm;
+    int sub;
+    xcd_tile_block((int)blockIdx.x, (tile0 & 7) ? 1 : (int)gridDim.x / per, per, tile, sub);
+    tile += tile0;
+    r0 = sub * rm;
+    return tile * TILE + r0 < b.S;
+}
+
+// a layer's state: its stream-major array in HBM (the `rm` rows of this block) <-> its LDS planes, all THREADS threads of the block
+template <int THREADS>
+__device__ __forceinline__ void gru_state_io(const LayerDesc &L, int rm, float *state, unsigned short *SP, int sw, bool load)
+{
+    const int n = rm * L.n;
+    for (int e = (int)threadIdx.x; e < n; e += THREADS) {
+        const int row = e / L.n, col = e - row * L.n;
+        if (load) store_split(SP, rm * sw, row * sw + col, state[e]);
+        else state[e] = load_split(SP, rm * sw, row * sw + col);
+    }
+}
+
+// vad output, 1 x nv, lane = stream (ref: src/rnn.rs:359): the vad state of row `lane` sits at column c0 of matrix X (plane stride ps, row
+// stride w); `live`: the rows' live flags of that frame
+__device__ __forceinline__ float rnn_vad_out(const RnnPlan &pl, const float *__restrict__ fpar, const unsigned short *X, int ps, int w, int c0,
+                                             int lane, const int *live, const float *tab)
+{
+    float acc = fpar[pl.vo_b];
+    for (int k = 0; k < pl.vad.n; k++) acc = fmaf(fpar[pl.vo_w + k], load_split(X, ps, lane * w + c0 + k), acc);
+    return live[lane] ? activate(pl.act_vo, acc * (1.0f / 256.0f), tab) : 0.0f;
+}
+
+// gain `v` of (row, band) of frame f (ref: src/rnn.rs:378) and its smoothing g = max(g, 0.6 lastg) (ref: src/denoise.rs:106-109); a silent
+// frame (`lv` false) has gains 0 and leaves lastg alone
+__device__ __forceinline__ void rnn_gain_out(const Buffers &b, int f, int tile, int row, int band, bool lv, float v)
+{
+    const float gr = lv ? v : 0.0f;
+    NNN_TIF(b, g_raw, NB, f, tile, row)[(size_t)band * TILE] = gr;
+    float gs = 0.0f;
+    if (lv) {
+        float *lg = NNN_TI(b.lastg, NB, tile, row) + (size_t)band * TILE;
+        gs = fmaxf(gr, 0.6f * *lg);
+        *lg = gs;
+    }
+    NNN_TIF(b, g, NB, f, tile, row)[(size_t)band * TILE] = gs;
 }
 
 struct RnnLds {
@@ -220,17 +277,6 @@ __device__ __forceinline__ void gru_layer(const Buffers &b, const LayerDesc &L, 
         NNN_STAMP(b, 26);
     }
     lds_barrier();
-}
-
-// a layer's state: its stream-major array in HBM (the rows of this block) <-> its LDS planes, all threads of the block
-__device__ __forceinline__ void gru_state_io(const LayerDesc &L, int rm, float *state, unsigned short *SP, int sw, bool load)
-{
-    const int n = rm * L.n;
-    for (int e = (int)threadIdx.x; e < n; e += 64 * RNN_WAVES) {
-        const int row = e / L.n, col = e - row * L.n;
-        if (load) store_split(SP, rm * sw, row * sw + col, state[e]);
-        else state[e] = load_split(SP, rm * sw, row * sw + col);
-    }
 }
 
 // dense layer on the matrix cores: act(W x + b) for every (neuron block, 16-stream block) unit, units dealt round-robin to
@@ -332,47 +378,61 @@ __device__ __forceinline__ void features_row(const Buffers &b, int f, int tile, 
 //     registers and LDS, the cepstral ring and its pair distances in LDS; the last wave prepares frame f + 1's features
 //     while the others are inside frame f's GRU GEMMs (when the layer shapes leave it without a unit).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int rnn_state_w(const LayerDesc &L) { return 32 * L.rec.ksteps + 8; }
-// dynamic LDS of k_rnn (mirrors its carve-up): tanh table (256 floats) + live flags (2 x 64 ints), 3 bf16 planes of the
-// input matrix, the r * state matrix, the three state matrices and the feature staging for `rows` streams, the cepstral
-// ring and its pair distances ((8 x 22 + 28) x `rows` floats)
-inline size_t rnn_lds_bytes(const RnnPlan &pl, int rows)
+// byte offsets into k_rnn's dynamic LDS at `rows` stream rows per block: tanh table (256 floats), live flags of this frame and the next
+// (2 x 64 ints); 3 bf16 planes each of the input matrix, the r * state matrix, the three state matrices and the feature staging; the
+// cepstral ring [8 * 22][rows] and its pair distances [28][rows].  The kernel takes its pointers from it, the host the total.
+struct RnnLdsAt {
+    int tab, live, IN, RS, SPv, SPn, SPdn, FS, crs, dc, total;
+    int sw_v, sw_n, sw_dn;   // row strides of the state matrices
+};
+__host__ __device__ constexpr RnnLdsAt rnn_lds(const RnnPlan &pl, int rows)
 {
-    auto sw = [](const LayerDesc &L) { return (size_t)(32 * L.rec.ksteps + 8); };
-    const size_t cols = (size_t)pl.in_w + pl.rec_w + sw(pl.vad) + sw(pl.noise) + sw(pl.dn) + FS_W;
-    return (256 + 128) * 4 + (size_t)3 * rows * cols * 2 + (size_t)(CEPS_MEM * NB + 28) * rows * 4;
+    RnnLdsAt o{};
+    o.sw_v = rnn_state_w(pl.vad); o.sw_n = rnn_state_w(pl.noise); o.sw_dn = rnn_state_w(pl.dn);
+    int at = 0;
+    o.tab = lds_take(at, 256 * 4);
+    o.live = lds_take(at, 2 * 64 * 4);
+    o.IN = lds_take(at, 3 * rows * pl.in_w * 2);
+    o.RS = lds_take(at, 3 * rows * pl.rec_w * 2);
+    o.SPv = lds_take(at, 3 * rows * o.sw_v * 2);
+    o.SPn = lds_take(at, 3 * rows * o.sw_n * 2);
+    o.SPdn = lds_take(at, 3 * rows * o.sw_dn * 2);
+    o.FS = lds_take(at, 3 * rows * FS_W * 2);
+    o.crs = lds_take(at, CEPS_MEM * NB * rows * 4);
+    o.dc = lds_take(at, 28 * rows * 4);
+    o.total = at;
+    return o;
 }
+static_assert(rnn_lds(BkShapeBuiltin::plan(), 16).total == 66816 && rnn_lds(BkShapeBuiltin::plan(), 32).total == 132096, "k_rnn's LDS for the built-in shape class");
 
 __global__ void __launch_bounds__(64 * RNN_WAVES) k_rnn(Buffers b, RnnPlan pl, const uint4 *__restrict__ Wq,
                                                           const float *__restrict__ fpar, int tile0, int rm, int g)
 {
     HIP_DYNAMIC_SHARED(float, lds_raw)
+    char *ldsb = (char *)lds_raw;
     const int wave0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane0 = threadIdx.x & 63;
     int wave = wave0, lane = lane0, tid = threadIdx.x;
-    const int per = TILE / rm, mbt = rm >> 4;
-    int tile, sub;
-    xcd_tile_block((int)blockIdx.x, (tile0 & 7) ? 1 : (int)gridDim.x / per, per, tile, sub);
-    tile += tile0;                                         // tile0: first tile of this model's run
-    const int r0 = sub * rm;                               // first row of the tile handled here
-    if (tile * TILE + r0 >= b.S) return;   // (a block whose streams are all padding -- the last tile of a batch that is not a multiple of 64 -- has nothing to do)
+    const int mbt = rm >> 4;
+    int tile, r0;                                          // r0: first row of the tile handled here
+    if (!rnn_block_rows(b, tile0, rm, tile, r0)) return;
     // (... or all held, nnn_batch_hold_streams.  A block with live rows also runs its held rows, whose feature rows k_fft_xp -- which returns
     // by four streams -- may not have written in this call: stale or creation-time zeros.  Rows never mix here -- each GEMM row is its own
     // input row times the shared weights, the live flags are per row -- and a held row's results go to its own dead state.  DESIGN.md section 13.)
     if (!live_any(b, tile, r0, rm)) return;
     const bool rowl = lane < rm;                           // lane = stream phases: this lane has a row
     const int trow = r0 + (rowl ? lane : 0);               // its row in the tile
-    // ---- LDS carve-up (rnn_lds_bytes, above the kernel, mirrors it for the host)
-    float *tab = lds_raw;
-    int *live = (int *)(lds_raw + 256), *live_next = live + 64;
-    unsigned short *IN = (unsigned short *)(lds_raw + 256 + 128);
+    // ---- LDS
+    const RnnLdsAt o = rnn_lds(pl, rm);
+    float *tab = (float *)(ldsb + o.tab);
+    int *live = (int *)(ldsb + o.live), *live_next = live + 64;
+    unsigned short *IN = (unsigned short *)(ldsb + o.IN), *RS = (unsigned short *)(ldsb + o.RS);
     const int in_ps = rm * pl.in_w, rs_ps = rm * pl.rec_w;
-    unsigned short *RS = IN + 3 * in_ps;
-    const int sw_v = rnn_state_w(pl.vad), sw_n = rnn_state_w(pl.noise), sw_dn = rnn_state_w(pl.dn);
-    unsigned short *SPv = RS + 3 * rs_ps, *SPn = SPv + 3 * rm * sw_v, *SPdn = SPn + 3 * rm * sw_n;
-    unsigned short *FS = SPdn + 3 * rm * sw_dn;
-    float *crs = (float *)(FS + 3 * rm * FS_W);        // cepstral ring [8 * 22][rm]
-    float *dc = crs + CEPS_MEM * NB * rm;              // pair distances [28][rm]
+    const int sw_v = o.sw_v, sw_n = o.sw_n, sw_dn = o.sw_dn;
+    unsigned short *SPv = (unsigned short *)(ldsb + o.SPv), *SPn = (unsigned short *)(ldsb + o.SPn), *SPdn = (unsigned short *)(ldsb + o.SPdn);
+    unsigned short *FS = (unsigned short *)(ldsb + o.FS);
+    float *crs = (float *)(ldsb + o.crs);              // cepstral ring [8 * 22][rm]
+    float *dc = (float *)(ldsb + o.dc);                // pair distances [28][rm]
     RnnLds lds{tab, live, IN, RS, in_ps, rs_ps, rm};
     float *sv = b.gru_v + ((size_t)tile * TILE * b.gru_v_w + (size_t)r0 * pl.vad.n),
           *sn = b.gru_n + ((size_t)tile * TILE * b.gru_n_w + (size_t)r0 * pl.noise.n),
@@ -391,7 +451,7 @@ __global__ void __launch_bounds__(64 * RNN_WAVES) k_rnn(Buffers b, RnnPlan pl, c
     // ---- once per launch: zero every operand plane (padding columns must read as 0), activation table, ring, states
     {
         uint4 *z = (uint4 *)IN;
-        const int n16 = (int)(((char *)crs - (char *)IN) / 16);
+        const int n16 = (o.crs - o.IN) / 16;
         for (int i = tid; i < n16; i += 64 * RNN_WAVES) z[i] = make_uint4(0u, 0u, 0u, 0u);
         for (int i = tid; i < 201; i += 64 * RNN_WAVES) tab[i] = b.tansig[i];
         const float *cm = NNN_TI(b.ceps_mem, CEPS_MEM * NB, tile, trow);
@@ -409,9 +469,10 @@ __global__ void __launch_bounds__(64 * RNN_WAVES) k_rnn(Buffers b, RnnPlan pl, c
         }
     }
     lds_barrier();
-    gru_state_io(pl.vad, rm, sv, SPv, sw_v, true);
-    gru_state_io(pl.noise, rm, sn, SPn, sw_n, true);
-    gru_state_io(pl.dn, rm, sdn, SPdn, sw_dn, true);
+    constexpr int T = 64 * RNN_WAVES;
+    gru_state_io<T>(pl.vad, rm, sv, SPv, sw_v, true);
+    gru_state_io<T>(pl.noise, rm, sn, SPn, sw_n, true);
+    gru_state_io<T>(pl.dn, rm, sdn, SPdn, sw_dn, true);
     if (rowl)
         for (int p = wave; p < 28; p += RNN_WAVES) dc[p * rm + lane] = pair_dist(crs, p, lane, rm);
     int mem_id = (wave == RNN_WAVES - 1 && rowl) ? NNN_TI(b.mem_id, 1, tile, trow)[0] : 0;
@@ -455,36 +516,21 @@ __global__ void __launch_bounds__(64 * RNN_WAVES) k_rnn(Buffers b, RnnPlan pl, c
 #define NNN_GRU_DN(M) gru_layer<M>(b, pl.dn, pl, lds, SPdn, sw_dn, Wq, fpar, wave, lane, feat_next);
         NNN_MB(mb_v, NNN_GRU_V)                                             // ref: src/rnn.rs:356-358
         NNN_STAMP(b, 12);
-        if (wave == RNN_WAVES - 1 && rowl) {   // vad output, 1 x nv, lane = stream (ref: src/rnn.rs:359)
-            float acc = fpar[pl.vo_b];
-            for (int k = 0; k < pl.vad.n; k++) acc = fmaf(fpar[pl.vo_w + k], load_split(IN, in_ps, lane * pl.in_w + pl.cV + k), acc);
-            NNN_TIF(b, vad, 1, f, tile, trow)[0] = live[lane] ? activate(pl.act_vo, acc * (1.0f / 256.0f), tab) : 0.0f;
-        }
+        if (wave == RNN_WAVES - 1 && rowl) NNN_TIF(b, vad, 1, f, tile, trow)[0] = rnn_vad_out(pl, fpar, IN, in_ps, pl.in_w, pl.cV, lane, live, tab);
         NNN_MB(mb_n, NNN_GRU_N)                                             // ref: src/rnn.rs:361-366
         NNN_STAMP(b, 13);
         NNN_MB(mb_dn, NNN_GRU_DN)                                           // ref: src/rnn.rs:368-377
         NNN_STAMP(b, 14);
-        // gains (ref: src/rnn.rs:378) and smoothing g = max(g, 0.6 lastg) (ref: src/denoise.rs:106-109)
-        dense_layer(pl.out, pl, lds, Wq, fpar, wave, lane, [&](int lrow, int band, float v) {
-            const int row = r0 + lrow;
-            const bool lv = live[lrow] != 0;
-            const float gr = lv ? v : 0.0f;
-            NNN_TIF(b, g_raw, NB, f, tile, row)[(size_t)band * TILE] = gr;
-            float gs = 0.0f;
-            if (lv) {
-                float *lg = NNN_TI(b.lastg, NB, tile, row) + (size_t)band * TILE;
-                gs = fmaxf(gr, 0.6f * *lg);
-                *lg = gs;
-            }
-            NNN_TIF(b, g, NB, f, tile, row)[(size_t)band * TILE] = gs;
-        });
+        // gains and their smoothing
+        dense_layer(pl.out, pl, lds, Wq, fpar, wave, lane,
+                    [&](int lrow, int band, float v) { rnn_gain_out(b, f, tile, r0 + lrow, band, live[lrow] != 0, v); });
         feat_next();   // layer shapes that keep every wave busy: the next frame's features go last
         NNN_STAMP(b, 15);
     }
     // ---- states back to HBM (the last layer's update is behind its closing barrier)
-    gru_state_io(pl.vad, rm, sv, SPv, sw_v, false);
-    gru_state_io(pl.noise, rm, sn, SPn, sw_n, false);
-    gru_state_io(pl.dn, rm, sdn, SPdn, sw_dn, false);
+    gru_state_io<T>(pl.vad, rm, sv, SPv, sw_v, false);
+    gru_state_io<T>(pl.noise, rm, sn, SPn, sw_n, false);
+    gru_state_io<T>(pl.dn, rm, sdn, SPdn, sw_dn, false);
     if (wave == RNN_WAVES - 1 && rowl) NNN_TI(b.mem_id, 1, tile, trow)[0] = mem_id;
 #undef NNN_MB
 }

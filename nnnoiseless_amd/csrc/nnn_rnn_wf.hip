@@ -1,6 +1,6 @@
 #pragma once
-// nnn_rnn_wf.hip -- K10w, the layer-pipelined RNN: k_rnn_wf and everything only it uses.  Not a translation unit: nnn_kernels.hip includes it
-// between k_rnn (nnn_rnn.hip, whose GEMM and layer pieces it uses) and the synthesis.
+// nnn_rnn_wf.hip -- K10w, the layer-pipelined RNN: k_rnn_wf, its LDS layout (wf_lds) and everything only it uses.  Not a translation unit:
+// nnn_kernels.hip includes it between k_rnn (nnn_rnn.hip, whose GEMM and shared layer pieces it uses) and the synthesis.
 
 namespace nnn {
 
@@ -262,15 +262,38 @@ struct WfPlan {   // LDS strides (bf16 elements) of the per-layer matrices, set 
 __host__ __device__ constexpr WfPlan wf_plan_of(const RnnPlan &pl)
 {
     return WfPlan{32 * pl.vad.in.ksteps + 8, 32 * pl.noise.in.ksteps + 8, 32 * pl.dn.in.ksteps + 8,
-                  32 * pl.vad.rec.ksteps + 8, 32 * pl.noise.rec.ksteps + 8, 32 * pl.dn.rec.ksteps + 8};
+                  rnn_state_w(pl.vad), rnn_state_w(pl.noise), rnn_state_w(pl.dn)};
 }
-// the layer-pipelined kernel's dynamic LDS (mirrors k_rnn_wf's carve-up)
-inline size_t rnn_wf_lds_bytes(const WfPlan &w)
+// byte offsets into k_rnn_wf's dynamic LDS: tanh table (256 floats); live flags [8][16] (frame f at slot f mod 8: written a tick before the
+// first reader, read until three ticks after); 3 bf16 planes each of the vad input, the noise input (2 frame slots), the denoise input (3),
+// the three state and the three r * state matrices and the feature staging; the cepstral ring [8 * 22][16], its pair distances [28][16] and
+// the features wave's own cepstrum + pitch-correlation DCT [28][16].  The kernel takes its pointers from it, the host the total.
+struct WfLds { int tab, live, Xv, Xn, Xdn, SPv, SPn, SPdn, RSv, RSn, RSdn, FS, crs, dc, cnb, total; };
+__host__ __device__ constexpr WfLds wf_lds(const WfPlan &w)
 {
-    const size_t cols = (size_t)w.w_v + 2 * w.w_n + 3 * w.w_dn + 2 * ((size_t)w.sw_v + w.sw_n + w.sw_dn) + WF_FS_W;
-    return (256 + 128) * 4 + (size_t)3 * WF_ROWS * cols * 2 + (size_t)(CEPS_MEM * NB + 28 + 28) * WF_ROWS * 4;
+    constexpr int plane3 = 3 * WF_ROWS * 2;   // bytes per column of a three-plane matrix
+    WfLds o{};
+    int at = 0;
+    o.tab = lds_take(at, 256 * 4);
+    o.live = lds_take(at, 8 * WF_ROWS * 4);
+    o.Xv = lds_take(at, plane3 * w.w_v);
+    o.Xn = lds_take(at, 2 * plane3 * w.w_n);
+    o.Xdn = lds_take(at, 3 * plane3 * w.w_dn);
+    o.SPv = lds_take(at, plane3 * w.sw_v);
+    o.SPn = lds_take(at, plane3 * w.sw_n);
+    o.SPdn = lds_take(at, plane3 * w.sw_dn);
+    o.RSv = lds_take(at, plane3 * w.sw_v);
+    o.RSn = lds_take(at, plane3 * w.sw_n);
+    o.RSdn = lds_take(at, plane3 * w.sw_dn);
+    o.FS = lds_take(at, plane3 * WF_FS_W);
+    o.crs = lds_take(at, CEPS_MEM * NB * WF_ROWS * 4);
+    o.dc = lds_take(at, 28 * WF_ROWS * 4);
+    o.cnb = lds_take(at, 28 * WF_ROWS * 4);
+    o.total = at;
+    return o;
 }
-// SH: a shape class with a compile-time packing plan (SH::plan(), e.g. BkShapeBuiltin of nnn_back.hip: every model of the built-in
+static_assert(wf_lds(wf_plan_of(BkShapeBuiltin::plan())).total == 127744, "k_rnn_wf's LDS for the built-in shape class");
+// SH: a shape class with a compile-time packing plan (SH::plan(), e.g. BkShapeBuiltin of nnn_layout.h: every model of the built-in
 // layer sizes) or WfShapeAny (the plan comes with the launch).  With a compile-time plan only the six activation kinds are taken from
 // the launch's plan: every stride, column and fragment offset is a constant -- the run-time form keeps some fifty of them in scalar
 // registers, more than the wave has, and pays for it in v_readlane / v_writelane spill traffic inside the tick loop (round 5: a sixth
@@ -297,28 +320,25 @@ __global__ void __launch_bounds__(64 * WF_WAVES, NNN_WF_MINWAVES) k_rnn_wf(Buffe
     const int wave0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane0 = threadIdx.x & 63;
     int wave = wave0, lane = lane0;
-    int tile, sub;
-    xcd_tile_block((int)blockIdx.x, (tile0 & 7) ? 1 : (int)gridDim.x / (TILE / rm), TILE / rm, tile, sub);
-    tile += tile0;
-    const int r0 = sub * rm;                                 // first row of the tile handled here
-    if (tile * TILE + r0 >= b.S) return;   // (a block whose streams are all padding -- the last tile of a batch that is not a multiple of 64 -- has nothing to do)
+    int tile, r0;                                            // r0: first row of the tile handled here
+    if (!rnn_block_rows(b, tile0, rm, tile, r0)) return;
     if (!live_any(b, tile, r0, rm)) return;   // (... or all held, nnn_batch_hold_streams; held rows beside live ones: see k_rnn)
     const bool rowl = lane0 < rm;
     const int trow = r0 + (rowl ? lane0 : 0);
     NNN_STAMP(b, 50);
-    // ---- LDS carve-up (rnn_wf_lds_bytes, above the kernel, mirrors it for the host)
-    float *tab = lds_raw;
-    int *live = (int *)(lds_raw + 256);                  // [8][16]: live flags of frame f at slot f mod 8 (written a tick before the
-                                                         // first reader, read until three ticks after)
-    unsigned short *Xv = (unsigned short *)(lds_raw + 256 + 128);
-    unsigned short *Xn = Xv + 3 * rm * wp.w_v;           // 2 slots
-    unsigned short *Xdn = Xn + 2 * 3 * rm * wp.w_n;      // 3 slots
-    unsigned short *SPv = Xdn + 3 * 3 * rm * wp.w_dn, *SPn = SPv + 3 * rm * wp.sw_v, *SPdn = SPn + 3 * rm * wp.sw_n;
-    unsigned short *RSv = SPdn + 3 * rm * wp.sw_dn, *RSn = RSv + 3 * rm * wp.sw_v, *RSdn = RSn + 3 * rm * wp.sw_n;
-    unsigned short *FS = RSdn + 3 * rm * wp.sw_dn;
-    float *crs = (float *)(FS + 3 * rm * WF_FS_W);       // cepstral ring [8 * 22][rm]
-    float *dc = crs + CEPS_MEM * NB * rm;                // pair distances [28][rm]
-    float *cnb = dc + 28 * rm;                           // the frame's own cepstrum + pitch-correlation DCT [28][rm] (features wave)
+    // ---- LDS
+    const WfLds o = wf_lds(wp);
+    // (a float base with offsets in floats, and below the zeroed span as a pointer difference, where k_rnn and k_back take a byte base
+    // and the span from the offsets: either of those here and the compiler orders k_rnn_wf<BkShapeBuiltin>'s instructions differently,
+    // and the headline kernel is kept instruction for instruction what it was)
+    auto planes = [&](int at) { return (unsigned short *)(lds_raw + at / 4); };   // (every offset is a whole number of 16-byte units)
+    float *tab = lds_raw + o.tab / 4;
+    int *live = (int *)(lds_raw + o.live / 4);
+    unsigned short *Xv = planes(o.Xv), *Xn = planes(o.Xn), *Xdn = planes(o.Xdn);
+    unsigned short *SPv = planes(o.SPv), *SPn = planes(o.SPn), *SPdn = planes(o.SPdn);
+    unsigned short *RSv = planes(o.RSv), *RSn = planes(o.RSn), *RSdn = planes(o.RSdn);
+    unsigned short *FS = planes(o.FS);
+    float *crs = lds_raw + o.crs / 4, *dc = lds_raw + o.dc / 4, *cnb = lds_raw + o.cnb / 4;
     const int cD = pl.dense.out_col, cV = pl.cV, cF = pl.cF;
     float *sv = b.gru_v + ((size_t)tile * TILE * b.gru_v_w + (size_t)r0 * pl.vad.n),
           *sn = b.gru_n + ((size_t)tile * TILE * b.gru_n_w + (size_t)r0 * pl.noise.n),
@@ -344,19 +364,12 @@ __global__ void __launch_bounds__(64 * WF_WAVES, NNN_WF_MINWAVES) k_rnn_wf(Buffe
         }
     }
     lds_barrier();
-    {
-        auto load_state = [&](const LayerDesc &L, const float *state, unsigned short *SP, int sw) {
-            for (int e = (int)threadIdx.x; e < rm * L.n; e += 64 * WF_WAVES) {
-                const int row = e / L.n, col = e - row * L.n;
-                store_split(SP, rm * sw, row * sw + col, state[e]);
-            }
-        };
-        load_state(pl.vad, sv, SPv, wp.sw_v);
-        load_state(pl.noise, sn, SPn, wp.sw_n);
-        load_state(pl.dn, sdn, SPdn, wp.sw_dn);
-        if (rowl)
-            for (int p = wave; p < 28; p += WF_WAVES) dc[p * rm + lane] = pair_dist(crs, p, lane, rm);
-    }
+    constexpr int T = 64 * WF_WAVES;
+    gru_state_io<T>(pl.vad, rm, sv, SPv, wp.sw_v, true);
+    gru_state_io<T>(pl.noise, rm, sn, SPn, wp.sw_n, true);
+    gru_state_io<T>(pl.dn, rm, sdn, SPdn, wp.sw_dn, true);
+    if (rowl)
+        for (int p = wave; p < 28; p += WF_WAVES) dc[p * rm + lane] = pair_dist(crs, p, lane, rm);
     int mem_id = wave == WF_WAVES - 1 ? NNN_TI(b.mem_id, 1, tile, r0 + (lane & 15))[0] : 0;   // every part of a row keeps a copy
     // this wave's GRU unit: its weights stay in registers for all ticks
     const int W_N = 6, W_V = 9, W_F = 11;   // first wave of the noise / vad roles; the features wave
@@ -391,25 +404,11 @@ __global__ void __launch_bounds__(64 * WF_WAVES, NNN_WF_MINWAVES) k_rnn_wf(Buffe
             WfDenseW<3> dw;   // the output layer reads the denoise state: <= 96 columns in this shape class
             const bool mine_o = on_o && wave - W_V < pl.out.nb;   // (the output layer has 22 neurons: two units, one per vad wave)
             if (on_v && wave - W_V < pl.vad.nb) wf_gru_a(pl.vad, Xv - cD, wp.w_v, SPv, RSv, wp.sw_v, Wq, wts, tab, wave - W_V, lane, ua);
-            if (mine_o) {   // gains of frame fo (ref: src/rnn.rs:378) and smoothing g = max(g, 0.6 lastg) (ref: src/denoise.rs:106-109)
+            if (mine_o) {   // gains of frame fo and their smoothing
                 const int *lv = live + 16 * (fo & 7);
-                {
-                    const int nbi = wave - W_V;
-                    wf_dense_load(dw, pl.out, Wq, fpar, wave - W_V, lane);
-                    wf_dense(pl.out, SPdn, wp.sw_dn, Wq, dw, tab, nbi, lane, [&](int lrow, int band, float v) {
-                        const int row = r0 + lrow;
-                        const bool on = lv[lrow] != 0;
-                        const float gr = on ? v : 0.0f;
-                        NNN_TIF(b, g_raw, NB, fo, tile, row)[(size_t)band * TILE] = gr;
-                        float gs = 0.0f;
-                        if (on) {
-                            float *lg = NNN_TI(b.lastg, NB, tile, row) + (size_t)band * TILE;
-                            gs = fmaxf(gr, 0.6f * *lg);
-                            *lg = gs;
-                        }
-                        NNN_TIF(b, g, NB, fo, tile, row)[(size_t)band * TILE] = gs;
-                    });
-                }
+                wf_dense_load(dw, pl.out, Wq, fpar, wave - W_V, lane);
+                wf_dense(pl.out, SPdn, wp.sw_dn, Wq, dw, tab, wave - W_V, lane,
+                         [&](int lrow, int band, float v) { rnn_gain_out(b, fo, tile, r0 + lrow, band, lv[lrow] != 0, v); });
             }
         } else {
             if (on_f) wf_features(b, wf_features_in(wts), ff, tile, r0, lane, crs, dc, cnb, FS, live + 16 * (ff & 7), mem_id);
@@ -468,12 +467,10 @@ __global__ void __launch_bounds__(64 * WF_WAVES, NNN_WF_MINWAVES) k_rnn_wf(Buffe
             }
         } else {
             if (on_n && rowl) {
-                // vad output of frame fn, 1 x nv, lane = stream (ref: src/rnn.rs:359), from the copy of that frame's vad state in
-                // the noise layer's input (columns 0.. of its window; not rewritten before tick fn + 2)
+                // vad output of frame fn, from the copy of that frame's vad state in the noise layer's input (columns 0.. of its window;
+                // not rewritten before tick fn + 2)
                 const unsigned short *Xv1 = Xn + (fn & 1) * 3 * rm * wp.w_n;
-                float acc = fpar[pl.vo_b];
-                for (int k = 0; k < pl.vad.n; k++) acc = fmaf(fpar[pl.vo_w + k], load_split(Xv1, rm * wp.w_n, lane * wp.w_n + k), acc);
-                NNN_TIF(b, vad, 1, fn, tile, trow)[0] = live[16 * (fn & 7) + lane] ? activate(pl.act_vo, acc * (1.0f / 256.0f), tab) : 0.0f;
+                NNN_TIF(b, vad, 1, fn, tile, trow)[0] = rnn_vad_out(pl, fpar, Xv1, rm * wp.w_n, wp.w_n, 0, lane, live + 16 * (fn & 7), tab);
             }
         }
         NNN_STAMPW(b, 33 + 5 * srole, t == 2 && srole >= 0);
@@ -484,17 +481,9 @@ __global__ void __launch_bounds__(64 * WF_WAVES, NNN_WF_MINWAVES) k_rnn_wf(Buffe
         NNN_STAMPW(b, 34 + 5 * srole, t == 2 && srole >= 0);
     }
     // ---- states back to HBM
-    {
-        auto save_state = [&](const LayerDesc &L, float *state, const unsigned short *SP, int sw) {
-            for (int e = (int)threadIdx.x; e < rm * L.n; e += 64 * WF_WAVES) {
-                const int row = e / L.n, col = e - row * L.n;
-                state[e] = load_split(SP, rm * sw, row * sw + col);
-            }
-        };
-        save_state(pl.vad, sv, SPv, wp.sw_v);
-        save_state(pl.noise, sn, SPn, wp.sw_n);
-        save_state(pl.dn, sdn, SPdn, wp.sw_dn);
-    }
+    gru_state_io<T>(pl.vad, rm, sv, SPv, wp.sw_v, false);
+    gru_state_io<T>(pl.noise, rm, sn, SPn, wp.sw_n, false);
+    gru_state_io<T>(pl.dn, rm, sdn, SPdn, wp.sw_dn, false);
     if (wave0 == WF_WAVES - 1 && rowl) NNN_TI(b.mem_id, 1, tile, trow)[0] = mem_id;   // (part 0 of every row)
     NNN_STAMP(b, 52);
 }
