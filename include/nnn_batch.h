@@ -262,6 +262,38 @@ int nnn_batch_synthesize_device(nnn_batch *b, const float *d_gains, const float 
 int nnn_batch_analyze_host(nnn_batch *b, const void *in, float *features, int32_t *silence, int n_frames, const nnn_pcm_layout *layout);
 int nnn_batch_synthesize_host(nnn_batch *b, const float *gains, const float *vad, void *out, int n_frames, const nnn_pcm_layout *layout);
 int nnn_batch_pending_frames(const nnn_batch *b);   /* frames analysed and not yet synthesised (0 = none) */
+/*
+ * VAD-only calls: process_frame's second return value without its first.  For hosts that use the voice-activity probability alone --
+ * active-speaker detection, endpointing, gating a recorder, picking the conference legs to mix -- the call runs the front of the frame and
+ * the network's VAD branch (input_dense, vad_gru, vad_output: src/rnn.rs:353-359) for up to nnn_batch_max_group_frames(b) consecutive
+ * frames of every stream, and nothing of the denoiser behind them: no noise or denoise GRU (src/rnn.rs:361-378, about 95 % of the
+ * network's multiply-adds), no pitch filter, no gain interpolation, no inverse transform, and neither spectrum through device memory.
+ *   d_vad[t * n_streams + s]     the value process_frame returns for frame t of stream s; exactly 0.0f on a silent frame
+ * `layout` describes d_in as nnn_batch_process_pcm_device reads it -- all three formats, channels, strides; discard_first must be 0 (there
+ * is no audio to drop).  Rows are 4-byte aligned.  A host with more than nnn_batch_max_group_frames(b) frames loops.
+ * State.  A VAD call = shift_and_filter_input + compute_frame_features + the VAD branch of RnnState::compute.  It advances the input
+ * history and biquad state, last_period / last_gain, the cepstral ring and mem_id, the VAD GRU state (which stays put on silent frames, as
+ * in the ordinary path) and the batch's frame count, by n_frames.  It neither reads nor writes synthesis_mem, lastg, or the noise and
+ * denoise GRU states: of a stream's record every field is what ordinary processing calls on the same input would leave, except
+ * NNN_STREAM_STATE_SYNTHESIS_MEM, _LASTG, _NOISE_GRU and _DENOISE_GRU, which keep their bytes.  Hence:
+ *   - a stream may alternate freely between VAD calls and ordinary calls, and its VAD sequence is the all-ordinary run's bit for bit
+ *     whatever the mix;
+ *   - the AUDIO of the first ordinary frames after VAD-only frames overlap-adds a stale synthesis_mem and runs the two big GRUs from
+ *     stale state: that audio is the caller's to discard or fade.
+ * Ordering and protocol are a split call's: one frame group, in order on the caller's stream (hip_stream NULL = the batch's own), never
+ * pipelined, the device call asynchronous; the host variant stages its input in one piece and waits.  Refused, changing nothing and
+ * before anything is enqueued: frames pending from an analyze (the usual text), a NULL d_in, d_vad or layout, a bad layout or
+ * discard_first != 0, n_frames outside [1, nnn_batch_max_group_frames(b)], a set nnn_batch_fault.
+ * Held streams (nnn_batch_hold_streams): no kernel reads their input (the host variant still copies the caller's whole span to the
+ * device, their samples with it), their d_vad entries are left as they were, their parked record does not change; live streams' bits
+ * are those of the same call with nothing held; a call with every stream held launches nothing and moves the
+ * frame count.  Grouped batches run every model's own VAD branch.  The frame log (nnn_batch_set_frame_log) is not written and its
+ * position does not move.  With taps on, NNN_TAP_VAD, _FEATURES, _SILENCE, _PITCH and the pitch chain's taps read as after a processing
+ * call; NNN_TAP_X, _P, _G, _G_RAW and _BRANCH are unspecified.
+ * The batch is the denoiser's: a VAD-only host still pays its scratch (nnn_batch_device_bytes); nnn_batch_opts.max_group_frames sizes it.
+ */
+int nnn_batch_vad_device(nnn_batch *b, const void *d_in, float *d_vad, int n_frames, const nnn_pcm_layout *layout, void *hip_stream);
+int nnn_batch_vad_host(nnn_batch *b, const void *in, float *vad, int n_frames, const nnn_pcm_layout *layout);
 int nnn_batch_synchronize(nnn_batch *b);
 /* 1 if a pitch workgroup of an earlier call ran out of patience waiting for the previous frame's result (the frames of a group
  * run side by side below 16 384 streams and hand the last pitch from workgroup to workgroup): the state of the affected streams

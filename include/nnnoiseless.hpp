@@ -161,6 +161,17 @@ class BatchDenoiser {
         check(nnn_batch_synthesize_host(b_.get(), gains, vad, out, n_frames, &layout));
     }
     int pending_frames() const { return nnn_batch_pending_frames(b_.get()); }
+    // VAD only (nnn_batch.h "VAD-only calls"): vad [n_frames][n_streams], the values process returns, for up to max_group_frames frames and
+    // without the denoiser -- no audio out; synthesis_mem, lastg and the noise / denoise GRU states keep their bytes.  `layout` describes the
+    // input (discard_first 0).  Device buffers, asynchronous; host buffers, staged in one piece and synchronous.
+    void vad_device(const void *d_in, float *d_vad, int n_frames, const nnn_pcm_layout &layout, void *hip_stream = nullptr)
+    {
+        check(nnn_batch_vad_device(b_.get(), d_in, d_vad, n_frames, &layout, hip_stream));
+    }
+    void vad_host(const void *in, float *vad, int n_frames, const nnn_pcm_layout &layout)
+    {
+        check(nnn_batch_vad_host(b_.get(), in, vad, n_frames, &layout));
+    }
     void synchronize() { check(nnn_batch_synchronize(b_.get())); }
     // true once a frame hand-off inside the pitch stage has failed (nnn_batch_fault): sticky until reset() / load_state(); for hosts
     // that synchronise their own HIP stream instead of calling synchronize()

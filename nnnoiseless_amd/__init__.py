@@ -385,6 +385,27 @@ class BatchDenoiser:
         """Frames analysed and not yet synthesised (0 = none)."""
         return int(self._lib.L.nnn_batch_pending_frames(self._h))
 
+    # ---- VAD only: the speech probability without the denoiser (include/nnn_batch.h "VAD-only calls") ----
+    def vad(self, x, fmt=None, channels=1, vad=None):
+        """The VAD of up to max_group_frames() frames and nothing else: x as process takes it (fmt None) or as process_pcm does (fmt,
+        channels) -> float32 [n_frames, n_streams], the values process would return.  No audio is produced; synthesis_mem, lastg and the
+        noise / denoise GRU states stay as they are.  `vad`, when handed in, is written in place: held streams' entries stay."""
+        x, fmt, channels, T, gstride = self._pcm_shape("vad", x, fmt, channels)
+        S = self.n_streams
+        vad = np.zeros((T, S), np.float32) if vad is None else vad
+        if not (isinstance(vad, np.ndarray) and vad.shape == (T, S) and vad.dtype == np.float32 and vad.flags.c_contiguous and vad.flags.writeable):
+            raise ValueError(f"vad: `vad` must be a writable C-contiguous float32 array of shape [{T}, {S}]")
+        L = _ffi.PcmLayout(fmt, channels, 0, 0, gstride, FRAME_SIZE * channels)
+        self._lib.check(self._lib.L.nnn_batch_vad_host(self._h, _ffi.ptr(x), _ffi.ptr(vad), T, C.byref(L)))
+        self.frames_done += T
+        return vad
+
+    def vad_device(self, d_in, d_vad, n_frames, fmt, channels, group_stride, frame_stride, hip_stream=0):
+        """Raw device pointers (ints), strides in elements of the format; asynchronous on hip_stream (0 = the batch's own stream)."""
+        L = _ffi.PcmLayout(fmt, channels, 0, 0, group_stride, frame_stride)
+        self._lib.check(self._lib.L.nnn_batch_vad_device(self._h, d_in, d_vad, n_frames, C.byref(L), hip_stream))
+        self.frames_done += n_frames
+
     def synchronize(self):
         self._lib.check(self._lib.L.nnn_batch_synchronize(self._h))
 

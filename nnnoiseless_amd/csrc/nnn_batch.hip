@@ -30,5 +30,6 @@ using namespace nnn;
 #include "nnn_batch_snapshot.hip"
 #include "nnn_batch_host.hip"
 #include "nnn_batch_split.hip"
+#include "nnn_batch_vad.hip"
 #include "nnn_batch_debug.hip"
 #include "nnn_train.hip"

@@ -87,7 +87,9 @@ static const char *kKernelNames[K_COUNT] = {"k_hp", "k_lpc", "k_pitch", "k_fft_x
 enum Stage { ST_HP, ST_PITCH, ST_FFT, ST_RNN, ST_SYN, ST_COUNT };
 // The two launches only the split calls make (launch_stage; no events, no schedule nodes: a split call is one group in order on one stream):
 // ST_FEAT ends nnn_batch_analyze_* (k_features, then the rows out), ST_GAINS begins nnn_batch_synthesize_* (the caller's gains in).
-enum SplitStage { ST_FEAT = ST_COUNT, ST_GAINS };
+// The two only the VAD calls make (nnn_batch_vad_*): ST_FFT_FEAT is the transform stage without the spectra's trip
+// to memory (k_fft_feat; k_fft_xp while the taps are on), ST_VAD the feature stage and the network up to the VAD output (k_features, k_vad).
+enum SplitStage { ST_FEAT = ST_COUNT, ST_GAINS, ST_FFT_FEAT, ST_VAD };
 struct SplitIo {                   // the caller's row buffers of a split call (device memory)
     float *features = nullptr;     // [n_frames][n_streams][42]
     int *silence = nullptr;        // [n_frames][n_streams]
@@ -209,6 +211,8 @@ struct nnn_batch {
         int tile0 = 0, ntiles = 0;
         size_t back_lds = 0, rnn16_lds = 0;   // dynamic LDS of k_back<true> / k_back<false>; 0 = the model is outside the kernel's shape class
         BkActs acts = {};
+        int vad_rows = 0, vad_mb = 0;         // k_vad: stream rows per block, stream blocks per GRU wave unit (plan_model_group)
+        size_t vad_lds = 0;
     };
     Paths paths;                   // as of now
     Paths created;                 // as the batch was created with (clone: depth, rows and kernel forms follow from it)

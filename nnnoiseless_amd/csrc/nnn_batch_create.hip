@@ -110,6 +110,16 @@ static nnn_batch::ModelGroup plan_model_group(const RnnPlan &pl, int ntiles, con
     while (G.rows > 16 && G.ntiles * (TILE / G.rows) < RNN_SMALL_BATCH_BLOCKS) G.rows /= 2;
     if (paths.rnn_rows && (size_t)rnn_lds(G.plan, paths.rnn_rows).total <= kLdsMax) G.rows = paths.rnn_rows;
     G.rnn_lds = (size_t)rnn_lds(G.plan, G.rows).total;
+    // k_vad (the VAD calls): the most rows whose operands fit half the LDS -- two blocks per compute unit, which its 99 registers (four
+    // waves per SIMD) allow -- failing that the LDS, and whose GRU units fit the eight waves.  The built-in shape class: a whole tile per
+    // block.  Wherever k_rnn fits, 16 rows of this do; if none did, vad_rows stays 0 and the VAD calls alone refuse (vad_check).
+    for (int half = 2; half >= 1 && !G.vad_rows; half--)
+        for (int rows = TILE; rows >= 16 && !G.vad_rows; rows /= 2)
+            if ((size_t)vad_lds(vad_plan_view(G.plan), rows).total <= kLdsMax / half && vad_gru_mb(G.plan, rows)) G.vad_rows = rows;
+    if (G.vad_rows) {
+        G.vad_mb = vad_gru_mb(G.plan, G.vad_rows);
+        G.vad_lds = (size_t)vad_lds(vad_plan_view(G.plan), G.vad_rows).total;
+    }
     // models of the built-in shape class run the layer-pipelined kernel (its fixed wave roles cover 2 / 2 / 3 / 6 neuron
     // blocks in the input dense / vad / noise / denoise layers)
     G.wp = wf_plan_of(G.plan);   // (strides of its per-layer matrices)

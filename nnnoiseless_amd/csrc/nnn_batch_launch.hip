@@ -93,12 +93,13 @@ static void plan_group(const nnn_batch *h, int g, GroupPlan &p)
     }
 }
 
-// The kernels launched with more dynamic LDS than a function may have by default -- every k_rnn, k_rnn_wf and k_back instantiation.
+// The kernels launched with more dynamic LDS than a function may have by default -- every k_rnn, k_rnn_wf and k_back instantiation, k_vad.
 // launch_stage takes them from these tables and nowhere else, and creation raises the limit of every kernel in them to the hardware's
 // 160 KB (raise_lds_limits): an instantiation cannot be launched without having had its limit raised.
 using RnnWfKernel = decltype(&k_rnn_wf<WfShapeAny>);
 using BackKernel = decltype(&k_back<true, BkShapeBuiltin>);
 static const auto kRnnKernel = &k_rnn;
+static const auto kVadKernel = &k_vad;
 static const RnnWfKernel kRnnWfKernels[2] = {k_rnn_wf<WfShapeAny>, k_rnn_wf<BkShapeBuiltin>};   // [the model is of the built-in shape class]
 static const BackKernel kBackFused[2][2] = {   // [X rides in k_pitch][some stream held]
     {k_back<true, BkShapeBuiltin, false, false>, k_back<true, BkShapeBuiltin, false, true>},
@@ -111,6 +112,7 @@ static std::vector<const void *> big_lds_kernels()
     for (const auto &by_held : kBackFused)
         for (BackKernel k : by_held) v.push_back((const void *)k);
     for (BackKernel k : kBackRnnAlone) v.push_back((const void *)k);
+    v.push_back((const void *)kVadKernel);
     return v;
 }
 
@@ -182,6 +184,17 @@ static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, cons
         break;
     case ST_GAINS:
         hipLaunchKernelGGL(k_gains_in, dim3(NT), dim3(GIN_T), 0, st, b, io->gains, io->vad, g);
+        break;
+    // the VAD calls' launches, untimed like the split calls' (the caller's VAD rows travel in the parameter table, as a processing call's do)
+    case ST_FFT_FEAT:
+        if (b.taps) hipLaunchKernelGGL(k_fft_xp, dim3(Sp * ug / FFT_SPB), dim3(64 * FFT_SPB), 0, st, b, sp0, g);   // (so that the X and P taps exist)
+        else hipLaunchKernelGGL(k_fft_feat, dim3(Sp * ug / FFT_SPB), dim3(64 * FFT_SPB), 0, st, b, sp0, g);
+        break;
+    case ST_VAD:
+        hipLaunchKernelGGL(k_features, dim3(NT), dim3(64 * FEAT_WAVES), 0, st, b, g);
+        for (const nnn_batch::ModelGroup &G : h->groups)   // one launch per resident model, as the RNN's
+            hipLaunchKernelGGL(kVadKernel, dim3((unsigned)(G.ntiles * (TILE / G.vad_rows))), dim3(64 * RNN_WAVES), G.vad_lds, st, b, sp0, G.plan, G.wq,
+                               G.fpar, G.tile0, G.vad_rows, G.vad_mb, g);
         break;
     }
 }

@@ -480,7 +480,8 @@ constexpr int FH_STRIDE = NNN_FH_STRIDE;   // floats between the feature head's 
 static_assert(FH_STRIDE >= NB, "");
 // XR (fused, one-frame calls): X and its band energies are in memory already -- computed by rider blocks of k_pitch's launch, which needs
 // nothing of what the pitch analysis finds (xt_rider) -- and are fetched instead of computed.
-template <bool WITH_P, bool FUSED = false, bool XR = false>
+// SPECTRA false (k_fft_feat, the VAD-only calls): nobody reads X and P behind this launch, and they are not stored.
+template <bool WITH_P, bool FUSED = false, bool XR = false, bool SPECTRA = true>
 __device__ __forceinline__ void transform_inputs(const Buffers &b, const StepParams *sp, int tile_in, int sub, FftLds &t, float2 *Z, float *part,
                                                  XpKeep *keep = nullptr)
 {
@@ -506,7 +507,7 @@ __device__ __forceinline__ void transform_inputs(const Buffers &b, const StepPar
     float2 *dx = b.X + (size_t)s * FSTR;
     if (XR) spectrum_load(dx, X, lane);
     else window_rfft<FUSED>(b, sx, w, t, Z, X, lane, !FUSED);
-    if (!XR && (!FUSED || b.taps)) spectrum_store(dx, X, lane);   // (fused: the spectra stay in registers; memory sees them for the parity taps only)
+    if (SPECTRA && !XR && (!FUSED || b.taps)) spectrum_store(dx, X, lane);   // (fused: the spectra stay in registers; memory sees them for the parity taps only)
     NNN_FUSED_RELAUNDER();
     float *vv = (float *)Z, *vc = vv + BSK_LEN;   // per-bin quantities of the band sums, skewed (bsk)
     float exv;
@@ -530,13 +531,14 @@ __device__ __forceinline__ void transform_inputs(const Buffers &b, const StepPar
     NNN_FUSED_RELAUNDER();
     float2 Y[8];
     if (FUSED) window_load(b.hist + (size_t)__builtin_amdgcn_readfirstlane(s) * hist_stride(b.nslot), ring, rb, lag, lane, spw);
-    if (FUSED) {   // (the window again, from the L2: sixteen registers less across the first transform and the band sums of a wave that has 128)
+    if (FUSED || !SPECTRA) {   // (the window again, from the L2: sixteen registers less across the first transform and the band sums of a wave that has 128;
+                               // k_fft_feat: without it two of X's values spill across the second transform at 96 registers)
 #pragma unroll
         for (int r = 0; r < 8; r++) w[r] = ((const float2 *)b.window_a)[(lane < FFT_P1 ? lane : FFT_P1 - 1) + FFT_P1 * r];
     }
     window_rfft<FUSED>(b, spw, w, t, Z, Y, lane, false);
     float2 *dp = b.P + (size_t)s * FSTR;
-    if (!FUSED || b.taps) spectrum_store_p(dp, Y, lane, b.taps != 0);
+    if (SPECTRA && (!FUSED || b.taps)) spectrum_store_p(dp, Y, lane, b.taps != 0);
 #pragma unroll
     for (int u = 0; u < 8; u++) {
         const int k = rfft_slot_bin(lane, u);
@@ -652,6 +654,23 @@ __global__ void __launch_bounds__(64 * FFT_SPB, NNN_FFT_MINWAVES) k_fft_xp(Buffe
     b = frame_view(b, frame);
     const int wave = threadIdx.x >> 6;
     transform_inputs<true>(b, sp + frame, tile, sub, t, Z[wave], part[wave]);
+}
+// k_fft_xp without the spectra's stores, for the calls that stop at the VAD (nnn_batch_vad_*): band energies, the
+// normalised correlation, the feature head (cn, silence) as k_fft_xp leaves them, bit for bit; X and P never reach memory.  Same blocks,
+// same LDS, same five waves per SIMD.  With the taps on the VAD calls launch k_fft_xp instead, so that the X and P taps exist.
+__global__ void __launch_bounds__(64 * FFT_SPB, NNN_FFT_MINWAVES) k_fft_feat(Buffers b, const StepParams *sp, int g)
+{
+    __shared__ __attribute__((aligned(16))) char tbuf[FFT_TABLES_SHORT];
+    FftLds &t = *(FftLds *)tbuf;
+    __shared__ float2 Z[FFT_SPB][NFFT_BUF];
+    __shared__ float part[FFT_SPB][3 * FH_STRIDE];
+    int frame, tile, sub;
+    fft_block(b, g, frame, tile, sub);
+    if (tile * TILE + sub * FFT_SPB >= b.S) return;
+    if (!live_any(b, tile, sub * FFT_SPB, FFT_SPB)) return;
+    b = frame_view(b, frame);
+    const int wave = threadIdx.x >> 6;
+    transform_inputs<true, false, false, false>(b, sp + frame, tile, sub, t, Z[wave], part[wave]);
 }
 
 // Rider blocks of a one-frame k_pitch launch (blocks `riders` ..): the frame's lag-0 transform X and its band energies, eight streams

@@ -202,7 +202,9 @@ struct RnnLds {
 // exactly) for all frames of the launch: recurrent operand of the GEMMs, read back by the owning wave for the update, and
 // rewritten by it -- a layer costs two barriers, and no state travels to HBM and back between frames.
 // `idle` runs on waves without a unit while the others are in the first GEMM phase (the next frame's features).
-template <int MB, class Idle>
+// KS: the k-steps whose weight fragments are requested up front and held in registers (24 registers per k-step; a GEMM of more k-steps
+// fetches the rest as it goes, see gemm_acc).  k_vad, whose layer has one k-step in the built-in shape class, asks for one.
+template <int MB, int KS = KSMAX, class Idle>
 __device__ __forceinline__ void gru_layer(const Buffers &b, const LayerDesc &L, const RnnPlan &pl, const RnnLds &lds, unsigned short *SP,
                                           int sw, const uint4 *__restrict__ Wq, const float *__restrict__ fpar,
                                           int wave, int lane, Idle &&idle)
@@ -217,12 +219,12 @@ __device__ __forceinline__ void gru_layer(const Buffers &b, const LayerDesc &L, 
     const uint4 *Bin = Wq + L.in.wofs + (size_t)nbi * 3 * L.in.ksteps * 64;
     const uint4 *Brec = Wq + L.rec.wofs + (size_t)nbi * 3 * L.rec.ksteps * 64;
     // all weight fragments of this layer start travelling now
-    Frags<3> f_in;
-    Frags<2> f_zr;
-    Frags<1> f_h;
-    load_frags<3, 0>(f_in, L.in, Bin, lane);
-    load_frags<2, 0>(f_zr, L.rec, Brec, lane);
-    load_frags<1, 2>(f_h, L.rec, Brec, lane);
+    Frags<3, KS> f_in;
+    Frags<2, KS> f_zr;
+    Frags<1, KS> f_h;
+    load_frags<3, 0, KS>(f_in, L.in, Bin, lane);
+    load_frags<2, 0, KS>(f_zr, L.rec, Brec, lane);
+    load_frags<1, 2, KS>(f_h, L.rec, Brec, lane);
     float bias[3];
 #pragma unroll
     for (int g = 0; g < 3; g++) bias[g] = (neuron < L.n) ? fpar[L.bias + g * L.n + neuron] : 0.0f;
@@ -235,8 +237,8 @@ __device__ __forceinline__ void gru_layer(const Buffers &b, const LayerDesc &L, 
 #pragma unroll
             for (int mb = 0; mb < MB; mb++) acc[g][mb] = f32x4{bias[g], bias[g], bias[g], bias[g]};
         }
-        gemm_acc<2, MB, 0>(acc, SP, sp_ps, sw, mb0, L.rec, Brec, lane, f_zr);   // (recurrent part first: the order k_rnn_wf uses)
-        gemm_acc<3, MB, 0>(acc, lds.IN, lds.in_ps, pl.in_w, mb0, L.in, Bin, lane, f_in);
+        gemm_acc<2, MB, 0, KS>(acc, SP, sp_ps, sw, mb0, L.rec, Brec, lane, f_zr);   // (recurrent part first: the order k_rnn_wf uses)
+        gemm_acc<3, MB, 0, KS>(acc, lds.IN, lds.in_ps, pl.in_w, mb0, L.in, Bin, lane, f_in);
         // r * state: the columns of this neuron block, plus (last block) the padding up to the GEMM's k range, as zeros
         const int kcols = 32 * L.rec.ksteps;
 #pragma unroll
@@ -258,7 +260,7 @@ __device__ __forceinline__ void gru_layer(const Buffers &b, const LayerDesc &L, 
     lds_barrier();   // r * state complete; every wave is done reading the old state planes
     NNN_STAMP(b, 18);
     if (mine) {
-        gemm_acc<1, MB, 2>(acc, lds.RS, lds.rs_ps, pl.rec_w, mb0, L.rec, Brec, lane, f_h);
+        gemm_acc<1, MB, 2, KS>(acc, lds.RS, lds.rs_ps, pl.rec_w, mb0, L.rec, Brec, lane, f_h);
         NNN_STAMP(b, 23);
         if (nvalid) {
 #pragma unroll
