@@ -70,6 +70,23 @@ extern "C" {
         frame_stride: usize,
         hip_stream: *mut c_void,
     ) -> c_int;
+    fn nnn_batch_network_device(
+        b: *mut RawBatch,
+        d_features: *const c_float,
+        d_silence: *const i32,
+        d_gains: *mut c_float,
+        d_vad: *mut c_float,
+        n_frames: c_int,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    fn nnn_batch_network_host(
+        b: *mut RawBatch,
+        features: *const c_float,
+        silence: *const i32,
+        gains: *mut c_float,
+        vad: *mut c_float,
+        n_frames: c_int,
+    ) -> c_int;
     fn nnn_batch_fault(b: *const RawBatch) -> c_int;
     fn nnn_batch_hold_streams(b: *mut RawBatch, streams: *const c_int, n: c_int) -> c_int;
     fn nnn_batch_resume_streams(b: *mut RawBatch, streams: *const c_int, n: c_int) -> c_int;
@@ -235,6 +252,34 @@ impl BatchDenoiser {
         hip_stream: *mut c_void,
     ) {
         let rc = nnn_batch_process_device(self.raw, d_in, d_out, d_vad, n_frames as c_int, stream_stride, frame_stride, hip_stream);
+        assert_eq!(rc, 0, "nnnoiseless-mi355x: backend error");
+    }
+    /// The network alone (`nnn_batch_network_host`): `features` `[n_frames][n_streams][42]` (and `silence` `[n_frames][n_streams]`, 0 / 1)
+    /// -> the raw gains `[n_frames][n_streams][22]` and `vad` `[n_frames][n_streams]` of every stream's resident model.  Moves the three
+    /// GRU states and nothing else; any `n_frames >= 1`.
+    pub fn network(&mut self, features: &[f32], silence: Option<&[i32]>, gains: &mut [f32], vad: &mut [f32], n_frames: usize) {
+        assert_eq!(features.len(), self.n * n_frames * 42);
+        assert_eq!(gains.len(), self.n * n_frames * 22);
+        assert_eq!(vad.len(), self.n * n_frames);
+        if let Some(s) = silence {
+            assert_eq!(s.len(), self.n * n_frames);
+        }
+        let sil = silence.map_or(std::ptr::null(), |s| s.as_ptr());
+        let rc = unsafe { nnn_batch_network_host(self.raw, features.as_ptr(), sil, gains.as_mut_ptr(), vad.as_mut_ptr(), n_frames as c_int) };
+        assert_eq!(rc, 0, "nnnoiseless-mi355x: backend error");
+    }
+    /// Device-resident rows in the C call's order (see include/nnn_batch.h "Network-only calls"; `d_silence` / `d_vad` may be null);
+    /// asynchronous.
+    pub unsafe fn network_device(
+        &mut self,
+        d_features: *const f32,
+        d_silence: *const i32,
+        d_gains: *mut f32,
+        d_vad: *mut f32,
+        n_frames: usize,
+        hip_stream: *mut c_void,
+    ) {
+        let rc = nnn_batch_network_device(self.raw, d_features, d_silence, d_gains, d_vad, n_frames as c_int, hip_stream);
         assert_eq!(rc, 0, "nnnoiseless-mi355x: backend error");
     }
     /// True once a frame hand-off inside the pitch stage has failed (sticky until `reset`): for hosts that drive

@@ -294,6 +294,35 @@ int nnn_batch_pending_frames(const nnn_batch *b);   /* frames analysed and not y
  */
 int nnn_batch_vad_device(nnn_batch *b, const void *d_in, float *d_vad, int n_frames, const nnn_pcm_layout *layout, void *hip_stream);
 int nnn_batch_vad_host(nnn_batch *b, const void *in, float *vad, int n_frames, const nnn_pcm_layout *layout);
+/*
+ * Network-only calls: RnnState::compute (src/rnn.rs:343-379) on the caller's feature rows -- the piece of process_frame between
+ * nnn_batch_analyze_* and nnn_batch_synthesize_*, on every stream's own resident model.  For hosts that want the built-in (or a converted)
+ * network's gains in hand before the synthesis -- an attenuation limit, a per-band floor, a wet/dry blend --, for a bring-your-own-network
+ * host that still wants the VAD, and for scoring a model over stored feature rows.  n_frames x compute for every stream:
+ *   d_features[(t * n_streams + s) * 42 + k]   dense f32, as nnn_batch_analyze_* writes them
+ *   d_silence[t * n_streams + s]               0 / 1 as nnn_batch_analyze_* writes it; NULL = no frame is silent
+ *   d_gains[(t * n_streams + s) * 22 + band]   out: the RAW gains, rnn.compute's output (the value of NNN_TAP_G_RAW) -- no lastg smoothing,
+ *                                              which is the synthesize half's
+ *   d_vad[t * n_streams + s]                   out: the value process_frame returns; NULL = not wanted
+ * Rows are 4-byte aligned; the output rows must not overlap the input rows.  On a silent frame process_frame does not call the network
+ * (src/denoise.rs:100): the stream's three GRU states stay put, its gains row reads 22 x +0.0f and its VAD +0.0f.
+ * State.  The call reads and writes the VAD, noise and denoise GRU states and nothing else: not the input history, synthesis_mem, lastg,
+ * the cepstral ring, the pitch state, the frame log, a scratch set or a tap.  The frame count does not move (a fresh batch is still fresh
+ * for discard_first afterwards).  analyze -> network -> synthesize with the gains and VAD as they come is an ordinary processing call bit
+ * for bit, audio and state.
+ * Protocol.  Allowed with frames pending (nnn_batch_pending_frames is unchanged by it) and with none.  It uses no scratch set, so n_frames
+ * is any value >= 1, not bounded by nnn_batch_max_group_frames.  Ordering is a state call's: after every call made before it, before every
+ * call made after it, on the caller's stream (hip_stream NULL = the batch's own); never pipelined, the device call asynchronous.  The
+ * host variant stages its rows in one piece, waits, and copies rows back around held streams.
+ * Refused, changing nothing and before anything is enqueued: a NULL batch, d_features or d_gains, n_frames < 1, a misaligned row pointer,
+ * a set nnn_batch_fault.
+ * Held streams (nnn_batch_hold_streams): their feature and silence entries are not read (they may hold NaN), their gains and VAD entries
+ * are left as they were, their parked record does not change; live streams' bits are those of the same call with nothing held; a call with
+ * every stream held launches nothing.  Grouped batches run every model on its own streams.
+ */
+int nnn_batch_network_device(nnn_batch *b, const float *d_features, const int32_t *d_silence, float *d_gains, float *d_vad, int n_frames,
+                             void *hip_stream);
+int nnn_batch_network_host(nnn_batch *b, const float *features, const int32_t *silence, float *gains, float *vad, int n_frames);
 int nnn_batch_synchronize(nnn_batch *b);
 /* 1 if a pitch workgroup of an earlier call ran out of patience waiting for the previous frame's result (the frames of a group
  * run side by side below 16 384 streams and hand the last pitch from workgroup to workgroup): the state of the affected streams

@@ -172,6 +172,18 @@ class BatchDenoiser {
     {
         check(nnn_batch_vad_host(b_.get(), in, vad, n_frames, &layout));
     }
+    // Network only (nnn_batch.h "Network-only calls"): features [n_frames][n_streams][42] (silence [n_frames][n_streams], may be null) ->
+    // raw gains [n_frames][n_streams][22] and vad [n_frames][n_streams] (may be null) from every stream's resident model; moves the three
+    // GRU states and nothing else; any n_frames >= 1; allowed between analyze and synthesize.  Device buffers, asynchronous; host buffers,
+    // staged in one piece and synchronous.
+    void network_device(const float *d_features, const int32_t *d_silence, float *d_gains, float *d_vad, int n_frames, void *hip_stream = nullptr)
+    {
+        check(nnn_batch_network_device(b_.get(), d_features, d_silence, d_gains, d_vad, n_frames, hip_stream));
+    }
+    void network_host(const float *features, const int32_t *silence, float *gains, float *vad, int n_frames)
+    {
+        check(nnn_batch_network_host(b_.get(), features, silence, gains, vad, n_frames));
+    }
     void synchronize() { check(nnn_batch_synchronize(b_.get())); }
     // true once a frame hand-off inside the pitch stage has failed (nnn_batch_fault): sticky until reset() / load_state(); for hosts
     // that synchronise their own HIP stream instead of calling synchronize()

@@ -406,6 +406,33 @@ class BatchDenoiser:
         self._lib.check(self._lib.L.nnn_batch_vad_device(self._h, d_in, d_vad, n_frames, C.byref(L), hip_stream))
         self.frames_done += n_frames
 
+    # ---- network only: features in, raw gains and VAD out (include/nnn_batch.h "Network-only calls") ----
+    def network(self, features, silence=None, gains=None, vad=None):
+        """RnnState::compute of every stream's resident model on feature rows: features float32 [n_frames, n_streams, 42] (silence int32
+        [n_frames, n_streams] as analyze returns it, None: no frame is silent) -> (raw gains float32 [n_frames, n_streams, 22], vad
+        [n_frames, n_streams]).  Any n_frames >= 1; allowed between analyze and synthesize; moves the three GRU states and nothing else.
+        `gains` / `vad`, when handed in, are written in place: held streams' rows stay."""
+        features = _ffi.as_f32(features)
+        S = self.n_streams
+        if features.ndim != 3 or features.shape[0] < 1 or features.shape[1:] != (S, NB_FEATURES):
+            raise ValueError(f"network needs features of shape [n_frames >= 1, {S}, {NB_FEATURES}], got {features.shape}")
+        T = features.shape[0]
+        if silence is not None:
+            silence = np.ascontiguousarray(silence, dtype=np.int32)
+            if silence.shape != (T, S):
+                raise ValueError(f"network: `silence` must have shape [{T}, {S}], got {silence.shape}")
+        gains = np.zeros((T, S, NB_BANDS), np.float32) if gains is None else gains
+        vad = np.zeros((T, S), np.float32) if vad is None else vad
+        for a, shp, name in ((gains, (T, S, NB_BANDS), "gains"), (vad, (T, S), "vad")):
+            if not (isinstance(a, np.ndarray) and a.shape == shp and a.dtype == np.float32 and a.flags.c_contiguous and a.flags.writeable):
+                raise ValueError(f"network: `{name}` must be a writable C-contiguous float32 array of shape {list(shp)}")
+        self._lib.check(self._lib.L.nnn_batch_network_host(self._h, _ffi.ptr(features), _ffi.ptr(silence), _ffi.ptr(gains), _ffi.ptr(vad), T))
+        return gains, vad
+
+    def network_device(self, d_features, d_silence, d_gains, d_vad, n_frames, hip_stream=0):
+        """Raw device pointers (ints; d_silence and d_vad may be None); asynchronous on hip_stream (0 = the batch's own stream)."""
+        self._lib.check(self._lib.L.nnn_batch_network_device(self._h, d_features, d_silence, d_gains, d_vad, n_frames, hip_stream))
+
     def synchronize(self):
         self._lib.check(self._lib.L.nnn_batch_synchronize(self._h))
 

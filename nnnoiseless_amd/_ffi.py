@@ -24,7 +24,7 @@ BATCH_SYMBOLS = [
     "nnn_batch_reset_streams", "nnn_batch_export_streams", "nnn_batch_import_streams", "nnn_batch_export_streams_device",
     "nnn_batch_import_streams_device", "nnn_batch_hold_streams", "nnn_batch_resume_streams", "nnn_batch_num_held", "nnn_batch_held_mask",
     "nnn_batch_analyze_device", "nnn_batch_synthesize_device", "nnn_batch_analyze_host", "nnn_batch_synthesize_host", "nnn_batch_pending_frames",
-    "nnn_batch_vad_device", "nnn_batch_vad_host",
+    "nnn_batch_vad_device", "nnn_batch_vad_host", "nnn_batch_network_device", "nnn_batch_network_host",
 ]
 TRAIN_SYMBOLS = [
     "nnn_train_create", "nnn_train_destroy", "nnn_train_reset", "nnn_train_process_device", "nnn_train_process_host",
@@ -169,6 +169,9 @@ class Library:
         if hasattr(L, "nnn_batch_vad_device"):
             L.nnn_batch_vad_device.argtypes = [vp, vp, vp, i32, C.POINTER(PcmLayout), vp]
             L.nnn_batch_vad_host.argtypes = [vp, vp, vp, i32, C.POINTER(PcmLayout)]
+        if hasattr(L, "nnn_batch_network_device"):
+            L.nnn_batch_network_device.argtypes = [vp, vp, vp, vp, vp, i32, vp]
+            L.nnn_batch_network_host.argtypes = [vp, vp, vp, vp, vp, i32]
         if hasattr(L, "nnn_node_hold_streams"):
             ip = C.POINTER(i32)
             L.nnn_node_hold_streams.argtypes = [vp, ip, i32]

@@ -31,5 +31,6 @@ using namespace nnn;
 #include "nnn_batch_host.hip"
 #include "nnn_batch_split.hip"
 #include "nnn_batch_vad.hip"
+#include "nnn_batch_network.hip"
 #include "nnn_batch_debug.hip"
 #include "nnn_train.hip"

@@ -213,6 +213,8 @@ struct nnn_batch {
         BkActs acts = {};
         int vad_rows = 0, vad_mb = 0;         // k_vad: stream rows per block, stream blocks per GRU wave unit (plan_model_group)
         size_t vad_lds = 0;
+        int net_rows = 0;                     // k_net (the network calls): stream rows per block, its dynamic LDS (plan_model_group)
+        size_t net_lds = 0;
     };
     Paths paths;                   // as of now
     Paths created;                 // as the batch was created with (clone: depth, rows and kernel forms follow from it)

@@ -120,6 +120,11 @@ static nnn_batch::ModelGroup plan_model_group(const RnnPlan &pl, int ntiles, con
         G.vad_mb = vad_gru_mb(G.plan, G.vad_rows);
         G.vad_lds = (size_t)vad_lds(vad_plan_view(G.plan), G.vad_rows).total;
     }
+    // k_net (the network calls): 16 rows per block unless NNN_RNN_ROWS says otherwise -- two blocks per compute unit (114 registers, 48 KB
+    // of LDS each for the built-in class) beat one block of 32 rows at every size measured.  Its LDS is k_rnn's
+    // minus 1152 bytes per row, so whatever fits there fits here.
+    G.net_rows = paths.rnn_rows && (size_t)net_lds(G.plan, paths.rnn_rows).total <= kLdsMax ? paths.rnn_rows : 16;
+    G.net_lds = (size_t)net_lds(G.plan, G.net_rows).total;
     // models of the built-in shape class run the layer-pipelined kernel (its fixed wave roles cover 2 / 2 / 3 / 6 neuron
     // blocks in the input dense / vad / noise / denoise layers)
     G.wp = wf_plan_of(G.plan);   // (strides of its per-layer matrices)

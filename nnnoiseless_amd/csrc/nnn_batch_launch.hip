@@ -93,13 +93,14 @@ static void plan_group(const nnn_batch *h, int g, GroupPlan &p)
     }
 }
 
-// The kernels launched with more dynamic LDS than a function may have by default -- every k_rnn, k_rnn_wf and k_back instantiation, k_vad.
+// The kernels launched with more dynamic LDS than a function may have by default -- every k_rnn, k_rnn_wf and k_back instantiation, k_vad, k_net.
 // launch_stage takes them from these tables and nowhere else, and creation raises the limit of every kernel in them to the hardware's
 // 160 KB (raise_lds_limits): an instantiation cannot be launched without having had its limit raised.
 using RnnWfKernel = decltype(&k_rnn_wf<WfShapeAny>);
 using BackKernel = decltype(&k_back<true, BkShapeBuiltin>);
 static const auto kRnnKernel = &k_rnn;
 static const auto kVadKernel = &k_vad;
+static const auto kNetKernel = &k_net;   // (launched by nnn_batch_network_device, nnn_batch_network.hip)
 static const RnnWfKernel kRnnWfKernels[2] = {k_rnn_wf<WfShapeAny>, k_rnn_wf<BkShapeBuiltin>};   // [the model is of the built-in shape class]
 static const BackKernel kBackFused[2][2] = {   // [X rides in k_pitch][some stream held]
     {k_back<true, BkShapeBuiltin, false, false>, k_back<true, BkShapeBuiltin, false, true>},
@@ -113,6 +114,7 @@ static std::vector<const void *> big_lds_kernels()
         for (BackKernel k : by_held) v.push_back((const void *)k);
     for (BackKernel k : kBackRnnAlone) v.push_back((const void *)k);
     v.push_back((const void *)kVadKernel);
+    v.push_back((const void *)kNetKernel);
     return v;
 }
 

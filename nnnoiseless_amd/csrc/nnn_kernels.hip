@@ -24,6 +24,7 @@
 #include "nnn_rnn.hip"
 #include "nnn_rnn_wf.hip"
 #include "nnn_vad.hip"
+#include "nnn_net.hip"
 #include "nnn_synth.hip"
 #include "nnn_split.hip"
 
