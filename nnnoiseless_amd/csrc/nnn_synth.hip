@@ -43,10 +43,15 @@ __device__ __forceinline__ void interp_gain2(const float *ga, const float *gb, i
 struct BinConst { int band[8]; float frac[8]; };   // band: -1 = no gain there (bins from 400 up, empty slots)
 // PLAIN (round 5): the call's boundary format is process_frame's own -- f32 in the range of an i16, one channel -- known when the kernel is launched:
 // the conversions, the channel arithmetic and their branches are compiled out of the instantiation the bench and most device-buffer callers run.
-template <bool SMV_IO, bool PLAIN = false>
+// TRANSFORMED: called behind the inverse transform, ahead of the overlap-add.  Xr, Pk and the band quantities have been dead since the spectrum
+// went to LDS, and the transform's own registers are free again: k_synth requests its next frame's inputs there (see k_synth).  The fused
+// back end passes nothing.
+struct SynthNoHook { __device__ __forceinline__ void operator()() const {} };
+template <bool SMV_IO, bool PLAIN = false, class TRANSFORMED = SynthNoHook>
 __device__ __forceinline__ void synth_frame(const Buffers &b, const StepParams *sp, int f, int tile, int sl, int s, int lane, const FftLds &t, float2 *A,
                                          float *r, float2 (&Xr)[8], const float2 (&Pk)[8], float b_ex, float b_ep, float b_xp, float b_graw,
-                                         float b_g, float vadv, bool live, float *sm, float4 (&smq)[2], const BinConst *bc = nullptr)
+                                         float b_g, float vadv, bool live, float *sm, float4 (&smq)[2], const BinConst *bc = nullptr,
+                                         TRANSFORMED &&transformed = SynthNoHook())
 {
     if (SMV_IO) {
 #pragma unroll
@@ -165,6 +170,7 @@ __device__ __forceinline__ void synth_frame(const Buffers &b, const StepParams *
         whi[u] = on ? ((const float4 *)b.window_s)[FRAME / 4 + n] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
     fft480_regs<true, !SMV_IO>(zin, A, t.tw, lane);   // time samples: x[2n] = A[n].y, x[2n+1] = A[n].x
+    transformed();
     if (lane == 0 && vad_out && s < b.S) vad_out[s] = vadv;
     const bool quad_ok = ch == 1 && (((size_t)o) & (size_t)(4 * elem - 1)) == 0;
 #pragma unroll
@@ -195,11 +201,19 @@ __device__ __forceinline__ void synth_frame(const Buffers &b, const StepParams *
     wave_lds_sync();   // A is refilled by the next frame
 }
 
+// wait until every vector-memory access the wave has issued is complete (the tests' interpreter has none in flight)
+__device__ __forceinline__ void vm_wait_all()
+{
+#ifdef __HIPCC__
+    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) alone: expcnt and lgkmcnt at their maxima
+#endif
+}
+
 #ifndef NNN_SYN_MINWAVES
 #define NNN_SYN_MINWAVES 4
 #endif
 template <bool PLAIN>
-__global__ void __launch_bounds__(64 * FFT_SPB, NNN_SYN_MINWAVES) k_synth(Buffers b, const StepParams *sp0, int g)
+__global__ void __launch_bounds__(64 * FFT_SPB, NNN_SYN_MINWAVES) k_synth(Buffers b, const StepParams *__restrict__ sp0, int g)
 {
     __shared__ FftLds t;
     __shared__ float2 A_[FFT_SPB][NFFT_BUF];   // also the per-bin energies of the band renormalisation (before A is filled)
@@ -230,26 +244,54 @@ __global__ void __launch_bounds__(64 * FFT_SPB, NNN_SYN_MINWAVES) k_synth(Buffer
     // (a held stream beside live ones, nnn_batch_hold_streams, is handed to the frame body under a padding stream's index: like one, it
     // writes neither audio nor VAD nor frame log, and the caller's bytes stay as they were.  The mask is constant for the call.)
     const int s_out = live_stream(b, tile, sl) ? s : b.S_pad;
+    // The frame loop is software-pipelined.  Every global load of a frame is independent of the frame before it, so frame f + 1's inputs --
+    // the X and P rows, the five band quantities, the silence flag and the VAD -- are requested inside frame f, into the registers that
+    // held frame f's, and a frame starts on data that is on its way or there instead of on two trips to memory in a row (the silence flag's,
+    // then everything else's) that only the three other waves of the SIMD cover.  The request goes out behind the inverse transform
+    // (synth_frame's TRANSFORMED) and lands under the overlap-add and the next frame's head: the transform's last pass leaves no register
+    // free at four waves per SIMD (eight more live values there spill), the stretch behind it leaves forty.
+    // The element offsets of a frame's scratch set (NNN_TIF: set f lies f * S_pad * LEN behind set 0) are stepped from frame to frame as
+    // wave-uniform values; the addresses are formed where the loads are issued, from the laundered lane.  (sp0 is restrict-qualified -- no
+    // kernel writes the parameter table it reads -- so that a frame's parameters are scalar loads: as vector loads at the head of the
+    // frame they were counted behind the requests, and the wait for them waited for every request.)
+    const int sl_u = __builtin_amdgcn_readfirstlane(sl);   // (the wave's row, in a scalar register)
+    const size_t step1 = (size_t)b.S_pad, stepb = step1 * NB, stepx = step1 * FSTR;
+    size_t o1 = (size_t)tile * TILE + sl_u, ob = (size_t)tile * TILE * NB + sl_u, ox = o1 * FSTR;   // frame 0's
+    float2 Xr[8], Pr[8];
+    float b_ex, b_ep, b_xp, b_graw, b_g, vadv;
+    int silent;
+    // `on` false (behind the group's last frame): nothing is loaded, and nothing of the frame before stays live across the transform
+    auto fetch = [&](int ln, bool on) {
+        silent = 0;
+        vadv = b_ex = b_ep = b_xp = b_graw = b_g = 0.0f;
+#pragma unroll
+        for (int u = 0; u < 8; u++) Xr[u] = Pr[u] = make_float2(0.0f, 0.0f);
+        if (!on) return;
+        // in the order the frame's head asks for them (loads return in order): the silence flag, the band quantities, then the spectra
+        silent = b.silence[o1];
+        if (ln < NB) {
+            b_xp = b.exp_[ob + (size_t)ln * TILE];
+            b_graw = b.g_raw[ob + (size_t)ln * TILE];
+            b_ex = b.ex[ob + (size_t)ln * TILE];
+            b_ep = b.ep[ob + (size_t)ln * TILE];
+            b_g = b.g[ob + (size_t)ln * TILE];
+        }
+        vadv = b.vad[o1];
+        // (the spectra arrive as the transforms held them, (bin k, bin 480 - k) pairs in 16-byte loads: spectrum_load)
+        spectrum_load(b.X + ox, Xr, ln);
+        spectrum_load_p(b.P + ox, Pr, ln);
+    };
+    fetch(lane0, true);
     for (int f = 0; f < g; f++) {
         lane = launder_v(lane0);   // keep the frame loop's addresses inside the loop (see launder_v)
-        const size_t fo = (size_t)b.S_pad * (size_t)f;   // this frame's scratch set
-        const float2 *Xg = b.X + (fo + s) * FSTR, *Pg = b.P + (fo + s) * FSTR;
-        // every global load of this frame is independent of its own results: issue them all now.  The spectra arrive as the
-        // transforms held them, (bin k, bin 480 - k) pairs in 16-byte loads (spectrum_load)
-        const bool live = NNN_TIF(b, silence, 1, f, tile, sl)[0] == 0;
-        float2 Xr[8], Pr[8];
-        spectrum_load(Xg, Xr, lane);
-        spectrum_load_p(Pg, Pr, lane);
-        float b_ex = 0.0f, b_ep = 0.0f, b_xp = 0.0f, b_graw = 0.0f, b_g = 0.0f;
-        if (lane < NB) {
-            b_ex = NNN_TIF(b, ex, NB, f, tile, sl)[(size_t)lane * TILE];
-            b_ep = NNN_TIF(b, ep, NB, f, tile, sl)[(size_t)lane * TILE];
-            b_xp = NNN_TIF(b, exp_, NB, f, tile, sl)[(size_t)lane * TILE];
-            b_graw = NNN_TIF(b, g_raw, NB, f, tile, sl)[(size_t)lane * TILE];
-            b_g = NNN_TIF(b, g, NB, f, tile, sl)[(size_t)lane * TILE];
-        }
-        const float vadv = NNN_TIF(b, vad, 1, f, tile, sl)[0];
-        synth_frame<false, PLAIN>(b, sp0 + f, f, tile, sl, s_out, lane, t, A, r, Xr, Pr, b_ex, b_ep, b_xp, b_graw, b_g, vadv, live, sm, smq, &bc);
+        const bool live = silent == 0;
+        synth_frame<false, PLAIN>(b, sp0 + f, f, tile, sl, s_out, lane, t, A, r, Xr, Pr, b_ex, b_ep, b_xp, b_graw, b_g, vadv, live, sm, smq, &bc, [&]() {
+            // (the window quads, requested ahead of the transform, are the only loads still counted: have them waited for here, where they
+            // have long landed -- loads return in order, and a wait for them behind the requests below would wait for those too)
+            vm_wait_all();
+            o1 += step1; ob += stepb; ox += stepx;
+            fetch(lane, f + 1 < g);
+        });
     }
 #pragma unroll
     for (int u = 0; u < 2; u++)
