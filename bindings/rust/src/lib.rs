@@ -92,6 +92,9 @@ extern "C" {
     fn nnn_batch_resume_streams(b: *mut RawBatch, streams: *const c_int, n: c_int) -> c_int;
     fn nnn_batch_num_held(b: *const RawBatch) -> c_int;
     fn nnn_batch_held_mask(b: *const RawBatch, held: *mut u8, n: usize) -> c_int;
+    fn nnn_batch_set_gain_floor(b: *mut RawBatch, streams: *const c_int, n: c_int, floors: *const c_float, bands: c_int) -> c_int;
+    fn nnn_batch_get_gain_floor(b: *mut RawBatch, streams: *const c_int, n: c_int, floors: *mut c_float) -> c_int;
+    fn nnn_batch_num_floored(b: *const RawBatch) -> c_int;
     fn nnn_host_alloc(bytes: usize) -> *mut c_void;
     fn nnn_host_free(p: *mut c_void);
     fn nnn_model_from_rnnoise_text(text: *const u8, len: usize) -> *mut RawModel;
@@ -163,6 +166,11 @@ impl Default for RnnModel {
         RnnModel(unsafe { nnn_model_default() })
     }
 }
+/// The gain floor of an attenuation limit: "never take a band down by more than `db` dB" = `10^(-db / 20)` (`BatchDenoiser::set_gain_floor`).
+pub fn attenuation_limit_db(db: f32) -> f32 {
+    10f32.powf(-db / 20.0)
+}
+
 /// `#[derive(Clone)]` in the reference (src/rnn.rs:54): an independent copy of the parameters (`nnn_model_clone`).
 impl Clone for RnnModel {
     fn clone(&self) -> RnnModel {
@@ -302,6 +310,29 @@ impl BatchDenoiser {
     }
     pub fn num_held(&self) -> usize {
         unsafe { nnn_batch_num_held(self.raw) as usize }
+    }
+    /// Gain floors of the listed streams (`nnn_batch_set_gain_floor`): in every `process` a non-silent frame's raw network gain becomes
+    /// `max(gain, floor)` before the pitch filter and the smoothing see it.  `floors`: one value per listed stream (all its 22 bands) or
+    /// 22 per stream; 0 = off; [`attenuation_limit_db`] turns "never more than 18 dB down" into a floor.  Configuration, not state:
+    /// resets, imports, hold / resume leave the floors alone, `clone` copies them.  `Err` (nothing changed) on an index out of range, a
+    /// repeat, a length that is neither, or a floor outside [0, 1].
+    pub fn set_gain_floor(&mut self, streams: &[i32], floors: &[f32]) -> Result<(), ()> {
+        let bands = if !streams.is_empty() && floors.len() == streams.len() * 22 { 22 } else { 1 };
+        if floors.len() != streams.len() * bands {
+            return Err(());
+        }
+        let rc = unsafe { nnn_batch_set_gain_floor(self.raw, streams.as_ptr(), streams.len() as c_int, floors.as_ptr(), bands as c_int) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// `[streams.len() * 22]`: the listed streams' floors.
+    pub fn gain_floor(&self, streams: &[i32]) -> Result<Vec<f32>, ()> {
+        let mut f = vec![0f32; streams.len() * 22];
+        let rc = unsafe { nnn_batch_get_gain_floor(self.raw, streams.as_ptr(), streams.len() as c_int, f.as_mut_ptr()) };
+        if rc == 0 { Ok(f) } else { Err(()) }
+    }
+    /// Streams with any floor above 0.
+    pub fn num_floored(&self) -> usize {
+        unsafe { nnn_batch_num_floored(self.raw) as usize }
     }
     /// `[n_streams]`: which streams are held.
     pub fn held(&self) -> Vec<bool> {

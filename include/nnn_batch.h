@@ -173,6 +173,46 @@ int nnn_batch_num_held(const nnn_batch *b);
 int nnn_batch_held_mask(const nnn_batch *b, uint8_t *held, size_t n);    /* held[s] = 0 / 1 for s < n_streams; n >= n_streams */
 
 /*
+ * Gain floors: an attenuation limit inside the ordinary call ("never take a band down by more than 18 dB" is a floor of 10^(-18/20)).
+ * Every stream has 22 floors F[s][band] in [0, 1], all 0 -- off -- by default.  In every processing call (process_device / process_host /
+ * process_pcm_device / process_pcm_host, every format, interleave, discard_first, schedule and back end) the raw network gain of a
+ * non-silent frame becomes
+ *     g_raw = fmaxf(rnn output, F[s][band])
+ * before anything consumes it: the pitch filter (src/features.rs:223-257) sees the floored value, and so do the smoothing
+ * g = max(g_raw, 0.6 lastg) and lastg (src/denoise.rs:106-109).
+ *   - Silent frames are untouched: the reference applies no gains there and lastg stays.
+ *   - VAD and the three GRU states do not depend on gains: they are the unfloored run's, bit for bit.
+ *   - By definition an ordinary call under floors F equals nnn_batch_analyze_* -> nnn_batch_network_* -> max(gains, F) ->
+ *     nnn_batch_synthesize_*, bit for bit, in audio, VAD and every field of every exported record.
+ *   - NNN_TAP_G_RAW and NNN_TAP_G show the floored values.
+ * Not affected: nnn_batch_network_* keeps returning the raw, unfloored network output; nnn_batch_synthesize_* applies the caller's gains
+ * as given; nnn_batch_vad_*, nnn_batch_analyze_*, the training rows and the rnnoise_* surface are unchanged.
+ * Floors are configuration, not state.  They are not in the stream record (NNN_STREAM_STATE_VERSION stays 1) and not in the raw snapshot
+ * image (its size is unchanged, old snapshots still load).  How the other calls meet them:
+ *   nnn_batch_reset_streams, nnn_batch_import_streams[_device]   the floors stay
+ *   nnn_batch_hold_streams / nnn_batch_resume_streams             the floors stay; a held stream's floors may be set, and apply from its
+ *                                                                first frame after resume
+ *   nnn_batch_reset, nnn_batch_load_state                         the floors stay
+ *   nnn_batch_clone                                               the clone has the same floors
+ *   nnn_batch_export_streams[_device]                             the record of a floored stream imports anywhere: its lastg is simply >=
+ *                                                                the floor
+ * nnn_batch_set_gain_floor: floors[i * bands + k] for stream streams[i], bands = 1 (one value for all 22 bands of the stream) or 22; list
+ * and values in host memory.  Asynchronous, and ordered exactly as nnn_batch_import_streams is: on the batch's own stream, after every call
+ * made before and before every call made after (pipelined calls under nnn_batch_set_inputs_ready included); floors are constant for the
+ * whole of a processing call.  The FIRST set of a batch allocates the floor rows (88 bytes per stream, counted in nnn_batch_device_bytes
+ * from then on) and may stall the way the first hold does; a real-time host makes an empty set, nnn_batch_set_gain_floor(b, NULL, 0, NULL,
+ * 1), right after creating the batch, which allocates the rows and sets nothing.  nnn_batch_get_gain_floor waits for the batch's work and
+ * returns 22 values per listed stream (a set with bands = 1 reads back as 22 equal values; a batch that never set a floor: zeros; its list
+ * may repeat).  nnn_batch_num_floored: streams with any floor above 0.  A batch that never set a floor, or whose floors are all back to 0,
+ * runs exactly the kernels and instructions of a batch without floors.
+ * Both calls check everything first and refuse, changing nothing, on: a NULL batch; a NULL list or NULL values with n > 0; n < 0; an
+ * index outside [0, n_streams); a repeated index (set); bands other than 1 or 22; a floor that is NaN, below 0 or above 1.
+ */
+int nnn_batch_set_gain_floor(nnn_batch *b, const int *streams, int n, const float *floors, int bands);
+int nnn_batch_get_gain_floor(nnn_batch *b, const int *streams, int n, float *floors /* n * 22 */);
+int nnn_batch_num_floored(const nnn_batch *b);
+
+/*
  * n_frames x process_frame for every stream, buffers resident in device memory.
  *   sample i of frame t of stream s:  d_in [s * stream_stride + t * frame_stride + i]   (floats)
  *                                     d_out[s * stream_stride + t * frame_stride + i]   (may alias d_in)

@@ -80,6 +80,12 @@ int nnn_node_import_streams(nnn_node *n, const int *streams, int n_list, const v
 int nnn_node_hold_streams(nnn_node *n, const int *streams, int n_list);
 int nnn_node_resume_streams(nnn_node *n, const int *streams, int n_list);
 int nnn_node_num_held(const nnn_node *n);
+/* Gain floors by node-global index (nnn_batch_set_gain_floor / nnn_batch_get_gain_floor of the shards that own the streams; floors[i * bands
+ * + k] belongs to streams[i]; every shard's part of the list is checked before any shard is changed).  nnn_node_num_floored: streams with
+ * any floor above 0 over all shards. */
+int nnn_node_set_gain_floor(nnn_node *n, const int *streams, int n_list, const float *floors, int bands);
+int nnn_node_get_gain_floor(nnn_node *n, const int *streams, int n_list, float *floors /* n_list * 22 */);
+int nnn_node_num_floored(const nnn_node *n);
 /* 1 if any shard reports nnn_batch_fault */
 int nnn_node_fault(const nnn_node *n);
 

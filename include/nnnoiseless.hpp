@@ -14,6 +14,7 @@
 //
 // Everything runs in the HIP kernels behind include/nnn_batch.h; failures throw std::runtime_error.
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <memory>
@@ -227,6 +228,23 @@ class BatchDenoiser {
         check(nnn_batch_held_mask(b_.get(), m.data(), m.size()));
         return m;
     }
+    // gain floors (nnn_batch_set_gain_floor): in every processing call a non-silent frame's raw network gain becomes max(gain, floor) before
+    // the pitch filter and the smoothing see it.  floors: one value per listed stream (all its 22 bands) or 22 per stream; 0 = off.
+    // Configuration, not state: resets, imports, hold / resume and load_state leave the floors alone, clone() copies them.
+    static float attenuation_limit_db(float db) { return std::pow(10.0f, -db / 20.0f); }   // "never more than db dB down" as a floor
+    void set_gain_floor(const std::vector<int> &streams, const std::vector<float> &floors)
+    {
+        const int bands = floors.size() == streams.size() * 22 && !streams.empty() ? 22 : 1;
+        if (floors.size() != streams.size() * (size_t)bands) throw std::invalid_argument("set_gain_floor: 1 or 22 floors per listed stream");
+        check(nnn_batch_set_gain_floor(b_.get(), streams.data(), (int)streams.size(), floors.data(), bands));
+    }
+    std::vector<float> gain_floor(const std::vector<int> &streams) const   // [streams.size() * 22]
+    {
+        std::vector<float> f(streams.size() * 22);
+        check(nnn_batch_get_gain_floor(b_.get(), streams.data(), (int)streams.size(), f.data()));
+        return f;
+    }
+    int num_floored() const { return nnn_batch_num_floored(b_.get()); }
     // records in device memory, asynchronous on hip_stream (nullptr: the batch's own stream)
     void export_streams_device(const std::vector<int> &streams, void *d_dst, void *hip_stream = nullptr)
     {

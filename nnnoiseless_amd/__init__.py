@@ -34,6 +34,12 @@ from ._ffi import STREAM_STATE_BYTES, STREAM_STATE_VERSION, stream_state_field  
 _lib = None
 
 
+def attenuation_limit_db(db):
+    """The gain floor of an attenuation limit: "never take a band down by more than `db` dB" = 10 ** (-db / 20)
+    (BatchDenoiser.set_gain_floor)."""
+    return 10.0 ** (-float(db) / 20.0)
+
+
 def library():
     """The hipcc-built gfx950 library (loaded on first use)."""
     global _lib
@@ -237,6 +243,27 @@ class BatchDenoiser:
 
     def num_held(self):
         return int(self._lib.L.nnn_batch_num_held(self._h))
+
+    def set_gain_floor(self, idx, floors):
+        """Gain floors of the listed streams (include/nnn_batch.h nnn_batch_set_gain_floor): in every processing call a non-silent frame's
+        raw network gain becomes max(gain, floor) before the pitch filter and the smoothing see it.  floors: a scalar (every listed
+        stream, all 22 bands), [len(idx)] (one value per stream) or [len(idx), 22]; 0 = off; attenuation_limit_db(18) = "never more than
+        18 dB down".  Configuration, not state: floors survive resets, imports, hold / resume and load_state, and clone() copies them.
+        Enqueued in order with the processing calls; returns at once."""
+        a, p = _ffi.stream_list(idx)
+        f, bands = _ffi.gain_floors(floors, a.size)
+        self._lib.check(self._lib.L.nnn_batch_set_gain_floor(self._h, p, a.size, f.ctypes.data_as(C.POINTER(C.c_float)), bands))
+
+    def gain_floor(self, idx=None):
+        """float32 [len(idx), 22]: the listed streams' floors (idx=None: every stream's).  Waits for the batch's work."""
+        a, p = _ffi.stream_list(range(self.n_streams) if idx is None else idx)
+        out = np.zeros((a.size, NB_BANDS), np.float32)
+        self._lib.check(self._lib.L.nnn_batch_get_gain_floor(self._h, p, a.size, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def num_floored(self):
+        """Streams with any floor above 0."""
+        return int(self._lib.L.nnn_batch_num_floored(self._h))
 
     def export_streams_device(self, idx, d_dst, hip_stream=0):
         """Records into device memory at d_dst (an int, len(idx) * STREAM_STATE_BYTES bytes); asynchronous on hip_stream."""

@@ -25,6 +25,7 @@ BATCH_SYMBOLS = [
     "nnn_batch_import_streams_device", "nnn_batch_hold_streams", "nnn_batch_resume_streams", "nnn_batch_num_held", "nnn_batch_held_mask",
     "nnn_batch_analyze_device", "nnn_batch_synthesize_device", "nnn_batch_analyze_host", "nnn_batch_synthesize_host", "nnn_batch_pending_frames",
     "nnn_batch_vad_device", "nnn_batch_vad_host", "nnn_batch_network_device", "nnn_batch_network_host",
+    "nnn_batch_set_gain_floor", "nnn_batch_get_gain_floor", "nnn_batch_num_floored",
 ]
 TRAIN_SYMBOLS = [
     "nnn_train_create", "nnn_train_destroy", "nnn_train_reset", "nnn_train_process_device", "nnn_train_process_host",
@@ -38,6 +39,7 @@ NODE_SYMBOLS = [
     "nnn_node_process_host", "nnn_node_process_pcm_host", "nnn_node_process_device", "nnn_node_process_device_streams", "nnn_node_synchronize",
     "nnn_node_fault", "nnn_node_shard_cpus", "nnn_node_reset_streams", "nnn_node_export_streams", "nnn_node_import_streams",
     "nnn_node_hold_streams", "nnn_node_resume_streams", "nnn_node_num_held",
+    "nnn_node_set_gain_floor", "nnn_node_get_gain_floor", "nnn_node_num_floored",
 ]
 RNNOISE_SYMBOLS = [
     "rnnoise_get_frame_size", "rnnoise_get_size", "rnnoise_init", "rnnoise_create", "rnnoise_destroy",
@@ -172,6 +174,16 @@ class Library:
         if hasattr(L, "nnn_batch_network_device"):
             L.nnn_batch_network_device.argtypes = [vp, vp, vp, vp, vp, i32, vp]
             L.nnn_batch_network_host.argtypes = [vp, vp, vp, vp, vp, i32]
+        if hasattr(L, "nnn_batch_set_gain_floor"):
+            ip, fp = C.POINTER(i32), C.POINTER(C.c_float)
+            L.nnn_batch_set_gain_floor.argtypes = [vp, ip, i32, fp, i32]
+            L.nnn_batch_get_gain_floor.argtypes = [vp, ip, i32, fp]
+            L.nnn_batch_num_floored.argtypes = [vp]
+        if hasattr(L, "nnn_node_set_gain_floor"):
+            ip, fp = C.POINTER(i32), C.POINTER(C.c_float)
+            L.nnn_node_set_gain_floor.argtypes = [vp, ip, i32, fp, i32]
+            L.nnn_node_get_gain_floor.argtypes = [vp, ip, i32, fp]
+            L.nnn_node_num_floored.argtypes = [vp]
         if hasattr(L, "nnn_node_hold_streams"):
             ip = C.POINTER(i32)
             L.nnn_node_hold_streams.argtypes = [vp, ip, i32]
@@ -253,3 +265,16 @@ def stream_records(records, n):
     if r.size != n * STREAM_STATE_BYTES:
         raise ValueError(f"need {n} records of {STREAM_STATE_BYTES} bytes, got {r.size} bytes")
     return r.reshape(n, STREAM_STATE_BYTES)
+
+
+def gain_floors(floors, n):
+    """Floors for n listed streams as the float32 block the C ABI takes and its `bands`: a scalar (every listed stream, all bands), [n] (one
+    value per stream, all its bands) -> bands 1; [n, 22] -> bands 22."""
+    f = np.asarray(floors, dtype=np.float32)
+    if f.ndim == 0:
+        f = np.full(n, f, np.float32)
+    if f.shape == (n,):
+        return np.ascontiguousarray(f), 1
+    if f.shape == (n, 22):
+        return np.ascontiguousarray(f), 22
+    raise ValueError(f"floors must be a scalar, [{n}] or [{n}, 22], got shape {f.shape}")

@@ -326,7 +326,9 @@ __device__ __forceinline__ void bk_dense(const LayerDesc &L, const BkRnn &R, con
 struct BkActs { int dense, vad, noise, dn, out, vo; };   // activation kinds of the model at hand (ref: src/rnn.rs:242-250)
 // XR: the fused kernel of a one-frame call whose X transform rode in k_pitch's launch (transform_inputs, xt_rider).
 // HELD: some stream of the batch is held (nnn_batch_hold_streams) -- the instantiation that looks at the live mask; the launch plan picks it.
-template <bool FUSED, class SH, bool XR = false, bool HELD = false>
+// FLOOR: some stream of the batch has a gain floor (nnn_batch_set_gain_floor) -- the instantiation that reads b.gfloor; the launch plan picks
+// it only while nnn_batch_num_floored() > 0, so that every other batch runs the code it ran before floors existed.
+template <bool FUSED, class SH, bool XR = false, bool HELD = false, bool FLOOR = false>
 __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0, BkActs acts, const uint4 *__restrict__ Wq,
                                               const float *__restrict__ fpar, int tile0, int g)
 {
@@ -435,13 +437,17 @@ __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0,
         NNN_STAMP(b, 3);
         bk_features(b, f, tile, sl, wave, lane, pitch, silent, crs, dcw, cnw, FS, live, mem_id);
         NNN_STAMP(b, 4);
-        // the last gains of the rows and bands this lane smooths (the output layer's units), needed at the end of the RNN stretch
-        float lastg[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        // the last gains of the rows and bands this lane smooths (the output layer's units), needed at the end of the RNN stretch; with them
+        // (FLOOR) the same rows' and bands' gain floors
+        float lastg[4] = {0.0f, 0.0f, 0.0f, 0.0f}, gfl[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (wave < pl.out.nb) {
             const int band = wave * 16 + (lane & 15);
 #pragma unroll
             for (int q = 0; q < 4; q++)
-                if (band < NB) lastg[q] = NNN_TI(b.lastg, NB, tile, r0 + 4 * (lane >> 4) + q)[(size_t)band * TILE];
+                if (band < NB) {
+                    lastg[q] = NNN_TI(b.lastg, NB, tile, r0 + 4 * (lane >> 4) + q)[(size_t)band * TILE];
+                    if (FLOOR) gfl[q] = NNN_TI(b.gfloor, NB, tile, r0 + 4 * (lane >> 4) + q)[(size_t)band * TILE];
+                }
         }
         lds_barrier();   // every stream's features staged; the transforms' buffers are free: the RNN's operands take their space
         NNN_STAMP(b, 5);
@@ -497,6 +503,7 @@ __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0,
         bk_dense(pl.out, R, Wq, fpar, wave, lane, W, [&](int lrow, int band, float v, int q) {
             const int row = r0 + lrow;
             const bool lv = live[lrow] != 0;
+            if (FLOOR) v = fmaxf(v, q == 0 ? gfl[0] : (q == 1 ? gfl[1] : (q == 2 ? gfl[2] : gfl[3])));
             const float gr = lv ? v : 0.0f;
             NNN_TIF(b, g_raw, NB, f, tile, row)[(size_t)band * TILE] = gr;
             float gs = 0.0f;

@@ -25,6 +25,7 @@ using namespace nnn;
 // One file per concern, in dependency order: each part's header says what it needs from the parts above it.
 #include "nnn_batch_core.hip"
 #include "nnn_batch_streams.hip"
+#include "nnn_batch_floor.hip"
 #include "nnn_batch_launch.hip"
 #include "nnn_batch_create.hip"
 #include "nnn_batch_snapshot.hip"

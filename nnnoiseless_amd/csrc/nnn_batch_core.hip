@@ -170,6 +170,8 @@ struct GroupPlan {
     int hp = 0;                    // 0 = k_hp, 1 / 2 = k_hp2<1> / k_hp2<2>
     bool held = false;             // some stream is held (nnn_batch_hold_streams): the high-pass, pitch and back-end kernels in the instantiations that
                                    // look at the live mask (and feed held streams zeros); otherwise the code a batch without a mask runs
+    bool floor = false;            // some stream has a gain floor (nnn_batch_set_gain_floor): the back-end kernels in the instantiations that read the floor
+                                   // rows; otherwise the code a batch without floors runs
     bool head = false;             // k_hp2 also runs the LPC sums' head (and k_pitch<true> takes it)
     bool lpc_in_pitch = false;     // k_pitch<true> does the LPC analysis
     int lpc_fc = 0;                // otherwise: k_lpc with lpc_fc frames per wave behind the high-pass, 0 = k_lpc_wide (lpc_launch)
@@ -288,6 +290,16 @@ struct nnn_batch {
     unsigned long long *live = nullptr;   // device: Buffers::live of every scratch set's argument block
     std::vector<uint8_t> held;         // the host's copy of the mask, for checking arguments and for the host-buffer calls' copies back
     int n_held = 0;
+    // gain floors (nnn_batch_set_gain_floor): configuration, not state -- in no record and no snapshot, untouched by
+    // reset and load_state.  The rows are made on the first set and counted in device_bytes; the argument blocks point at them only while
+    // some floor is above 0 (Buffers::gfloor), so that a batch whose floors are all off runs what a batch without floors runs
+    float *gfloor = nullptr;           // device: TI [22] per stream
+    std::vector<float> gfloor_host;    // the host's copy, [S][22] (empty until the first set): what get returns and num_floored counts
+    int n_floored = 0;                 // streams with any floor > 0
+    GrowBuf<char> fl_stage;            // device: a set call's list and values (capacity in entries)
+    GrowBuf<char> fl_pin{nullptr, 0, MEM_PINNED};   // ... and their page-locked source
+    hipEvent_t ev_fl = nullptr;        // the last copy out of fl_pin is done
+    bool fl_busy = false;
     // split calls (nnn_batch_analyze_* / nnn_batch_synthesize_*): frames analysed and not yet synthesised, the
     // scratch sets they lie in and the ring slot of the first one
     int pending = 0, pending_set0 = 0, pending_slot = 0;

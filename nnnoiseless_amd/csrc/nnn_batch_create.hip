@@ -82,6 +82,9 @@ extern "C" void nnn_batch_destroy(nnn_batch *h)
     h->ss_idx_pin.release();
     if (h->ev_ss_idx) hipEventDestroy(h->ev_ss_idx);
     h->ss_stage.release();
+    h->fl_stage.release();
+    h->fl_pin.release();
+    if (h->ev_fl) hipEventDestroy(h->ev_fl);
     delete[] h->plan.rnn;
     for (int i = 0; i < NSTREAMS; i++)
         if (h->pool[i]) hipStreamDestroy(h->pool[i]);

@@ -70,6 +70,7 @@ static void plan_group(const nnn_batch *h, int g, GroupPlan &p)
     // k_hp on two waves per tile (recurrence | everything else, k_hp2): for launches that leave SIMDs empty; groups: two tiles per block
     const bool split = k.hp_split >= 0 ? k.hp_split != 0 : h->NT <= 256;
     p.hp = !split ? 0 : ((k.hp_tpb ? k.hp_tpb == 2 : (g > 1 && h->NT >= 8)) ? 2 : 1);
+    p.floor = h->n_floored > 0;   // (nnn_batch_set_gain_floor; the host's count is as the device's rows will be when the launch runs, like the mask's)
     p.held = h->n_held > 0;   // (the host's copy of the mask is as the device's will be when the launch runs: hold and resume are enqueued in call order)
     // One-frame groups of batches whose pitch launch is a single round of workgroups (two 8-wave blocks per compute unit) run the LPC
     // analysis inside k_pitch: one launch fewer on the critical path of a real-time tick (measured per one-frame call: -6 us at 4096
@@ -102,17 +103,23 @@ static const auto kRnnKernel = &k_rnn;
 static const auto kVadKernel = &k_vad;
 static const auto kNetKernel = &k_net;   // (launched by nnn_batch_network_device, nnn_batch_network.hip)
 static const RnnWfKernel kRnnWfKernels[2] = {k_rnn_wf<WfShapeAny>, k_rnn_wf<BkShapeBuiltin>};   // [the model is of the built-in shape class]
-static const BackKernel kBackFused[2][2] = {   // [X rides in k_pitch][some stream held]
-    {k_back<true, BkShapeBuiltin, false, false>, k_back<true, BkShapeBuiltin, false, true>},
-    {k_back<true, BkShapeBuiltin, true, false>, k_back<true, BkShapeBuiltin, true, true>}};
-static const BackKernel kBackRnnAlone[2] = {k_back<false, BkShapeBuiltin, false, false>, k_back<false, BkShapeBuiltin, false, true>};   // [some stream held]
+static const BackKernel kBackFused[2][2][2] = {   // [X rides in k_pitch][some stream held][some stream floored]
+    {{k_back<true, BkShapeBuiltin, false, false, false>, k_back<true, BkShapeBuiltin, false, false, true>},
+     {k_back<true, BkShapeBuiltin, false, true, false>, k_back<true, BkShapeBuiltin, false, true, true>}},
+    {{k_back<true, BkShapeBuiltin, true, false, false>, k_back<true, BkShapeBuiltin, true, false, true>},
+     {k_back<true, BkShapeBuiltin, true, true, false>, k_back<true, BkShapeBuiltin, true, true, true>}}};
+static const BackKernel kBackRnnAlone[2][2] = {   // [some stream held][some stream floored]
+    {k_back<false, BkShapeBuiltin, false, false, false>, k_back<false, BkShapeBuiltin, false, false, true>},
+    {k_back<false, BkShapeBuiltin, false, true, false>, k_back<false, BkShapeBuiltin, false, true, true>}};
 static std::vector<const void *> big_lds_kernels()
 {
     std::vector<const void *> v{(const void *)kRnnKernel};
     for (RnnWfKernel k : kRnnWfKernels) v.push_back((const void *)k);
     for (const auto &by_held : kBackFused)
-        for (BackKernel k : by_held) v.push_back((const void *)k);
-    for (BackKernel k : kBackRnnAlone) v.push_back((const void *)k);
+        for (const auto &by_floor : by_held)
+            for (BackKernel k : by_floor) v.push_back((const void *)k);
+    for (const auto &by_floor : kBackRnnAlone)
+        for (BackKernel k : by_floor) v.push_back((const void *)k);
     v.push_back((const void *)kVadKernel);
     v.push_back((const void *)kNetKernel);
     return v;
@@ -155,7 +162,7 @@ static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, cons
     case ST_FFT:
         if (p.back == BACK_FUSED) {   // the fused back end takes the place of this stage and the two behind it: one launch per resident model
             for (const nnn_batch::ModelGroup &G : h->groups)   // (riders: its X transform done by k_pitch's rider blocks, see xt_rider)
-                L.go(K_BACK, kBackFused[p.riders][p.held], dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.back_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
+                L.go(K_BACK, kBackFused[p.riders][p.held][p.floor], dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.back_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
             break;
         }
         L.go(K_FFT_XP, k_fft_xp, dim3(Sp * ug / FFT_SPB), dim3(64 * FFT_SPB), 0, b, sp0, g);
@@ -165,7 +172,7 @@ static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, cons
         for (size_t i = 0; i < h->groups.size(); i++) {   // one launch per resident model (a run of whole tiles)
             const nnn_batch::ModelGroup &G = h->groups[i];
             if (p.rnn[i] == RK_BACK)
-                L.go(K_RNN, kBackRnnAlone[p.held], dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.rnn16_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
+                L.go(K_RNN, kBackRnnAlone[p.held][p.floor], dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.rnn16_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
             else if (p.rnn[i] == RK_WF_BUILTIN || p.rnn[i] == RK_WF_ANY)
                 L.go(K_RNN, kRnnWfKernels[p.rnn[i] == RK_WF_BUILTIN], dim3((unsigned)(G.ntiles * (TILE / WF_ROWS))), dim3(64 * WF_WAVES), G.wf_lds, b, G.plan, G.wp,
                      G.wq, G.fpar, G.tile0, g);

@@ -1,5 +1,6 @@
 // nnn_batch_snapshot.hip -- whole-batch state images (state_bytes, save_state, load_state) and clone.
-// Needs nnn_batch_core.hip (quiesce), create_batch of nnn_batch_create.hip and hold_prepare of nnn_batch_streams.hip.
+// Needs nnn_batch_core.hip (quiesce), create_batch of nnn_batch_create.hip, hold_prepare of nnn_batch_streams.hip and floor_clone of
+// nnn_batch_floor.hip.
 #pragma once
 
 // ---- state snapshots: DenoiseState is Clone in the reference (src/denoise.rs:36) ------------------------------------
@@ -92,6 +93,11 @@ extern "C" nnn_batch *nnn_batch_clone(nnn_batch *h)
         }
         c->held = h->held;
         c->n_held = h->n_held;
+    }
+    if (floor_clone(c, h) != 0) {   // the same gain floors (configuration travels with a clone)
+        nnn_batch_destroy(c);
+        fail("copy of the gain floors failed");
+        return nullptr;
     }
     c->frame_count = h->frame_count;
     c->group_count = h->group_count;

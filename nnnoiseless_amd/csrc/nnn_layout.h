@@ -162,6 +162,9 @@ struct Buffers {
     int *mem_id;         // TI [1]
     float *synth_mem;    // SM [480]
     float *lastg;        // TI [22]
+    const float *gfloor; // TI [22]     per-stream gain floors (nnn_batch_set_gain_floor): a non-silent frame's raw gain is fmaxf(rnn output, floor)
+                         //             before anything reads it.  Configuration, not state.  Null -- a batch that never set a floor, or whose floors
+                         //             are all back to 0 -- means no floor anywhere.  Constant for a whole call.
     int *last_period;    // TI [1]
     float *last_gain;    // TI [1]
     float *gru_v, *gru_n, *gru_dn;  // SM, tile t at t * 64 * gru_*_w (the widest resident model), rows of the tile's own width

@@ -435,3 +435,44 @@ extern "C" int nnn_node_num_held(const nnn_node *n)
         for (const auto &s : n->shards) total += nnn_batch_num_held(s.b);
     return total;
 }
+
+// gain floors by node-global index (nnn_batch_set_gain_floor): every shard's part is checked before any shard is changed
+int nnn_batch_check_gain_floor(const nnn_batch *h, const int *streams, int n, const float *floors, int bands, bool set);   // nnn_batch_floor.hip
+extern "C" int nnn_node_set_gain_floor(nnn_node *n, const int *streams, int n_list, const float *floors, int bands)
+{
+    std::vector<std::vector<int>> local, at;
+    if (int rc = node_split(n, streams, n_list, local, at)) return rc;
+    if (n_list > 0 && !floors) return nnn_set_error("null floor values");
+    if (bands != 1 && bands != 22) return nnn_set_error("bands must be 1 or 22");
+    std::vector<std::vector<float>> parts(local.size());
+    for (size_t k = 0; k < local.size(); k++) {
+        for (size_t j = 0; j < at[k].size(); j++)
+            parts[k].insert(parts[k].end(), floors + (size_t)at[k][j] * bands, floors + (size_t)(at[k][j] + 1) * bands);
+        if (int rc = nnn_batch_check_gain_floor(n->shards[k].b, local[k].data(), (int)local[k].size(), parts[k].data(), bands, true)) return rc;
+    }
+    for (size_t k = 0; k < local.size(); k++)
+        if (!local[k].empty())
+            if (int rc = nnn_batch_set_gain_floor(n->shards[k].b, local[k].data(), (int)local[k].size(), parts[k].data(), bands)) return rc;
+    return 0;
+}
+extern "C" int nnn_node_get_gain_floor(nnn_node *n, const int *streams, int n_list, float *floors)
+{
+    std::vector<std::vector<int>> local, at;
+    if (int rc = node_split(n, streams, n_list, local, at)) return rc;
+    if (n_list > 0 && !floors) return nnn_set_error("null floor buffer");
+    std::vector<float> part;
+    for (size_t k = 0; k < local.size(); k++) {
+        if (local[k].empty()) continue;
+        part.resize(local[k].size() * 22);
+        if (int rc = nnn_batch_get_gain_floor(n->shards[k].b, local[k].data(), (int)local[k].size(), part.data())) return rc;
+        for (size_t j = 0; j < at[k].size(); j++) memcpy(floors + (size_t)at[k][j] * 22, part.data() + j * 22, 22 * sizeof(float));
+    }
+    return 0;
+}
+extern "C" int nnn_node_num_floored(const nnn_node *n)
+{
+    int total = 0;
+    if (n)
+        for (const auto &s : n->shards) total += nnn_batch_num_floored(s.b);
+    return total;
+}

@@ -172,9 +172,11 @@ __device__ __forceinline__ float rnn_vad_out(const RnnPlan &pl, const float *__r
 }
 
 // gain `v` of (row, band) of frame f (ref: src/rnn.rs:378) and its smoothing g = max(g, 0.6 lastg) (ref: src/denoise.rs:106-109); a silent
-// frame (`lv` false) has gains 0 and leaves lastg alone
+// frame (`lv` false) has gains 0 and leaves lastg alone.  A batch with gain floors (nnn_batch_set_gain_floor; b.gfloor is null without):
+// the raw gain of a non-silent frame is fmaxf(v, the stream's floor of the band) before the tap, the smoothing and k_synth see it
 __device__ __forceinline__ void rnn_gain_out(const Buffers &b, int f, int tile, int row, int band, bool lv, float v)
 {
+    if (b.gfloor) v = fmaxf(v, NNN_TI(b.gfloor, NB, tile, row)[(size_t)band * TILE]);
     const float gr = lv ? v : 0.0f;
     NNN_TIF(b, g_raw, NB, f, tile, row)[(size_t)band * TILE] = gr;
     float gs = 0.0f;

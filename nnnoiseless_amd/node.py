@@ -112,6 +112,22 @@ class NodeDenoiser:
     def num_held(self):
         return int(self._lib.L.nnn_node_num_held(self._h))
 
+    def set_gain_floor(self, idx, floors):
+        """Gain floors of node-global streams: a scalar, [len(idx)] or [len(idx), 22] (BatchDenoiser.set_gain_floor)."""
+        a, p = _ffi.stream_list(idx)
+        f, bands = _ffi.gain_floors(floors, a.size)
+        self._lib.check(self._lib.L.nnn_node_set_gain_floor(self._h, p, a.size, f.ctypes.data_as(C.POINTER(C.c_float)), bands))
+
+    def gain_floor(self, idx=None):
+        """float32 [len(idx), 22]: the listed node-global streams' floors (idx=None: every stream's)."""
+        a, p = _ffi.stream_list(range(self.n_streams) if idx is None else idx)
+        out = np.zeros((a.size, 22), np.float32)
+        self._lib.check(self._lib.L.nnn_node_get_gain_floor(self._h, p, a.size, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def num_floored(self):
+        return int(self._lib.L.nnn_node_num_floored(self._h))
+
     def export_streams(self, idx):
         """Portable records of node-global streams, uint8 [len(idx), STREAM_STATE_BYTES] (BatchDenoiser.export_streams)."""
         a, p = _ffi.stream_list(idx)
