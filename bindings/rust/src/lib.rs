@@ -95,6 +95,8 @@ extern "C" {
     fn nnn_batch_set_gain_floor(b: *mut RawBatch, streams: *const c_int, n: c_int, floors: *const c_float, bands: c_int) -> c_int;
     fn nnn_batch_get_gain_floor(b: *mut RawBatch, streams: *const c_int, n: c_int, floors: *mut c_float) -> c_int;
     fn nnn_batch_num_floored(b: *const RawBatch) -> c_int;
+    fn nnn_batch_set_channel_link(b: *mut RawBatch, channels: c_int, mode: c_int) -> c_int;
+    fn nnn_batch_get_channel_link(b: *const RawBatch, channels: *mut c_int, mode: *mut c_int) -> c_int;
     fn nnn_host_alloc(bytes: usize) -> *mut c_void;
     fn nnn_host_free(p: *mut c_void);
     fn nnn_model_from_rnnoise_text(text: *const u8, len: usize) -> *mut RawModel;
@@ -169,6 +171,17 @@ impl Default for RnnModel {
 /// The gain floor of an attenuation limit: "never take a band down by more than `db` dB" = `10^(-db / 20)` (`BatchDenoiser::set_gain_floor`).
 pub fn attenuation_limit_db(db: f32) -> f32 {
     10f32.powf(-db / 20.0)
+}
+
+/// `enum nnn_link_mode`: how the channels of a link group share one gain per band (`BatchDenoiser::set_channel_link`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum LinkMode {
+    Off = 0,
+    /// the largest of the channels' network outputs: a band is kept if any channel's network keeps it
+    Max = 1,
+    /// the smallest
+    Min = 2,
 }
 
 /// `#[derive(Clone)]` in the reference (src/rnn.rs:54): an independent copy of the parameters (`nnn_model_clone`).
@@ -333,6 +346,21 @@ impl BatchDenoiser {
     /// Streams with any floor above 0.
     pub fn num_floored(&self) -> usize {
         unsafe { nnn_batch_num_floored(self.raw) as usize }
+    }
+    /// Channel link (`nnn_batch_set_channel_link`): the streams of group `s / channels` -- the channels of one stereo or four-channel
+    /// group at the PCM boundary -- get one common gain per band, the largest or smallest of their network outputs, before the floor, the
+    /// pitch filter and the smoothing see it; silent frames and held streams neither give nor take.  `channels` 2 or 4; 1 or
+    /// `LinkMode::Off`: off.  Configuration, not state: resets, imports, hold / resume leave it alone, `clone` copies it.  `Err` (nothing
+    /// changed) on other channel counts, `n_streams % channels != 0`, pending frames or a set fault.
+    pub fn set_channel_link(&mut self, channels: usize, mode: LinkMode) -> Result<(), ()> {
+        let rc = unsafe { nnn_batch_set_channel_link(self.raw, channels as c_int, mode as c_int) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// `(channels, mode)` the next `process` runs under: `(1, LinkMode::Off)` while off.
+    pub fn channel_link(&self) -> (usize, LinkMode) {
+        let (mut ch, mut md): (c_int, c_int) = (1, 0);
+        unsafe { nnn_batch_get_channel_link(self.raw, &mut ch, &mut md) };
+        (ch as usize, match md { 1 => LinkMode::Max, 2 => LinkMode::Min, _ => LinkMode::Off })
     }
     /// `[n_streams]`: which streams are held.
     pub fn held(&self) -> Vec<bool> {

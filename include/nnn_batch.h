@@ -213,6 +213,43 @@ int nnn_batch_get_gain_floor(nnn_batch *b, const int *streams, int n, float *flo
 int nnn_batch_num_floored(const nnn_batch *b);
 
 /*
+ * Channel link: one gain per band for the channels of a stereo (or four-channel) group, inside the ordinary call.  Streams are interleaved
+ * channel groups at the PCM boundary -- stream s is channel s % channels of group s / channels -- and the reference denoises each channel
+ * on its own (src/signal.rs:102-104, src/nnnoiseless.rs:318-320), so left and right are attenuated differently from frame to frame and
+ * the stereo image wanders.  Linking is the standard cure: compute the gains per channel, apply one common gain per band to all of them.
+ * Linking is batch-wide: the streams of link group s / channels are linked, channels = 2 or 4; channels = 1 or NNN_LINK_OFF means off, the
+ * default.  For every frame t, link group G and band k, let A be the streams of G that are live (not held) and whose frame t is not
+ * silent.  For s in A the raw network gain becomes
+ *     g_raw[s][k] = fmaxf( OP over u in A of rnn output[u][k],  F[s][k] )
+ * with OP = max for NNN_LINK_MAX (speech-preserving: a band is kept if any channel's network keeps it), min for NNN_LINK_MIN, and F the
+ * stream's gain floor (0 without): link first, then each stream's own floor.  The result is formed before anything consumes it: the pitch
+ * filter, the smoothing g = max(g_raw, 0.6 lastg), lastg, NNN_TAP_G_RAW / NNN_TAP_G and the frame log all see the linked value.
+ *   - A silent frame contributes nothing and receives nothing: no gains are applied there and lastg stays, as in the reference.
+ *   - A held stream contributes nothing and receives nothing.
+ *   - A group with one member in A is unlinked for that frame.
+ *   - VAD and the three GRU states do not depend on gains: they are the unlinked run's, bit for bit.
+ *   - By definition an ordinary call under link (channels, mode) and floors F equals nnn_batch_analyze_* -> nnn_batch_network_* -> the
+ *     formula above applied to the returned gains with the returned silence flags -> nnn_batch_synthesize_*, bit for bit, in audio, VAD and
+ *     every field of every exported record, in every processing call, format, interleave, discard_first, schedule, back end and host
+ *     route.  Max and min of finite floats are exact and order-independent: no tolerance enters anywhere.
+ * Not affected: nnn_batch_network_* keeps returning the raw, unlinked network output; nnn_batch_synthesize_* applies the caller's gains as
+ * given; nnn_batch_vad_*, nnn_batch_analyze_*, the training rows and the rnnoise_* surface are unchanged.
+ * The link is configuration, not state: not in the stream record (NNN_STREAM_STATE_VERSION stays 1), not in the snapshot image; it
+ * survives nnn_batch_reset, nnn_batch_reset_streams, nnn_batch_import_streams[_device], hold / resume and nnn_batch_load_state, and
+ * nnn_batch_clone copies it.  A record exported from a linked batch imports anywhere.  The set call returns at once and is ordered exactly
+ * as nnn_batch_set_gain_floor is: after every call made before and before every call made after; the setting is constant for the whole of
+ * a processing call.  It allocates nothing.  A batch that never links, or whose link is off again, runs exactly the kernels and
+ * instructions of a batch without a link.  A mean is deliberately left out: with silent members its divisor varies, and a sum brings
+ * rounding order into a contract that is otherwise exact.
+ * nnn_batch_set_channel_link refuses, changing nothing, on: a NULL batch; channels other than 1, 2 or 4; a mode outside the enum;
+ * n_streams % channels != 0; frames pending from an nnn_batch_analyze_*; a set nnn_batch_fault.  nnn_batch_get_channel_link (either
+ * pointer may be NULL) returns what the next processing call runs under: (1, NNN_LINK_OFF) while off, however it was switched off.
+ */
+enum nnn_link_mode { NNN_LINK_OFF = 0, NNN_LINK_MAX = 1, NNN_LINK_MIN = 2 };
+int nnn_batch_set_channel_link(nnn_batch *b, int channels, int mode);
+int nnn_batch_get_channel_link(const nnn_batch *b, int *channels, int *mode);
+
+/*
  * n_frames x process_frame for every stream, buffers resident in device memory.
  *   sample i of frame t of stream s:  d_in [s * stream_stride + t * frame_stride + i]   (floats)
  *                                     d_out[s * stream_stride + t * frame_stride + i]   (may alias d_in)

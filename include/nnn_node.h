@@ -86,6 +86,11 @@ int nnn_node_num_held(const nnn_node *n);
 int nnn_node_set_gain_floor(nnn_node *n, const int *streams, int n_list, const float *floors, int bands);
 int nnn_node_get_gain_floor(nnn_node *n, const int *streams, int n_list, float *floors /* n_list * 22 */);
 int nnn_node_num_floored(const nnn_node *n);
+/* Channel link of every shard (nnn_batch_set_channel_link; every shard is checked before any is changed).  Link groups are node-global
+ * stream indices / channels, so the call also refuses if any shard's first stream is not a multiple of `channels`: a group would lie in two
+ * shards.  nnn_node_get_channel_link: the setting all shards share. */
+int nnn_node_set_channel_link(nnn_node *n, int channels, int mode);
+int nnn_node_get_channel_link(const nnn_node *n, int *channels, int *mode);
 /* 1 if any shard reports nnn_batch_fault */
 int nnn_node_fault(const nnn_node *n);
 

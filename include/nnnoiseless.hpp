@@ -245,6 +245,18 @@ class BatchDenoiser {
         return f;
     }
     int num_floored() const { return nnn_batch_num_floored(b_.get()); }
+    // channel link (nnn_batch_set_channel_link): the streams of group s / channels -- the channels of one stereo or four-channel group at the
+    // PCM boundary -- get one common gain per band, the largest (NNN_LINK_MAX) or smallest (NNN_LINK_MIN) of their network outputs, before
+    // the floor, the pitch filter and the smoothing see it; silent frames and held streams neither give nor take.  channels 2 or 4;
+    // channels 1 or NNN_LINK_OFF: off.  Configuration, not state: resets, imports, hold / resume and load_state leave it alone, clone()
+    // copies it.
+    void set_channel_link(int channels, nnn_link_mode mode = NNN_LINK_MAX) { check(nnn_batch_set_channel_link(b_.get(), channels, (int)mode)); }
+    std::pair<int, nnn_link_mode> channel_link() const   // (1, NNN_LINK_OFF) while off
+    {
+        int channels = 1, mode = NNN_LINK_OFF;
+        check(nnn_batch_get_channel_link(b_.get(), &channels, &mode));
+        return {channels, (nnn_link_mode)mode};
+    }
     // records in device memory, asynchronous on hip_stream (nullptr: the batch's own stream)
     void export_streams_device(const std::vector<int> &streams, void *d_dst, void *hip_stream = nullptr)
     {

@@ -265,6 +265,21 @@ class BatchDenoiser:
         """Streams with any floor above 0."""
         return int(self._lib.L.nnn_batch_num_floored(self._h))
 
+    def set_channel_link(self, channels, mode="max"):
+        """Link the channels of every stream group (include/nnn_batch.h nnn_batch_set_channel_link): streams s with the same s // channels
+        -- the channels of one stereo or four-channel group at the PCM boundary -- get one common gain per band, the largest ("max": a
+        band is kept if any channel's network keeps it) or the smallest ("min") of their network outputs, before the floor, the pitch
+        filter and the smoothing see it; silent frames and held streams neither give nor take.  channels 2 or 4; channels 1 or mode "off"
+        switches it off.  Configuration, not state: it survives resets, imports, hold / resume and load_state, and clone() copies it.
+        Takes effect from the next processing call; returns at once."""
+        self._lib.check(self._lib.L.nnn_batch_set_channel_link(self._h, int(channels), _ffi.link_mode(mode)))
+
+    def channel_link(self):
+        """(channels, mode) the next processing call runs under: (1, "off") while off."""
+        ch, md = C.c_int32(0), C.c_int32(0)
+        self._lib.check(self._lib.L.nnn_batch_get_channel_link(self._h, C.byref(ch), C.byref(md)))
+        return ch.value, _ffi.link_mode_name(md.value)
+
     def export_streams_device(self, idx, d_dst, hip_stream=0):
         """Records into device memory at d_dst (an int, len(idx) * STREAM_STATE_BYTES bytes); asynchronous on hip_stream."""
         a, p = _ffi.stream_list(idx)

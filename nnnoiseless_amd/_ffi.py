@@ -26,6 +26,7 @@ BATCH_SYMBOLS = [
     "nnn_batch_analyze_device", "nnn_batch_synthesize_device", "nnn_batch_analyze_host", "nnn_batch_synthesize_host", "nnn_batch_pending_frames",
     "nnn_batch_vad_device", "nnn_batch_vad_host", "nnn_batch_network_device", "nnn_batch_network_host",
     "nnn_batch_set_gain_floor", "nnn_batch_get_gain_floor", "nnn_batch_num_floored",
+    "nnn_batch_set_channel_link", "nnn_batch_get_channel_link",
 ]
 TRAIN_SYMBOLS = [
     "nnn_train_create", "nnn_train_destroy", "nnn_train_reset", "nnn_train_process_device", "nnn_train_process_host",
@@ -40,6 +41,7 @@ NODE_SYMBOLS = [
     "nnn_node_fault", "nnn_node_shard_cpus", "nnn_node_reset_streams", "nnn_node_export_streams", "nnn_node_import_streams",
     "nnn_node_hold_streams", "nnn_node_resume_streams", "nnn_node_num_held",
     "nnn_node_set_gain_floor", "nnn_node_get_gain_floor", "nnn_node_num_floored",
+    "nnn_node_set_channel_link", "nnn_node_get_channel_link",
 ]
 RNNOISE_SYMBOLS = [
     "rnnoise_get_frame_size", "rnnoise_get_size", "rnnoise_init", "rnnoise_create", "rnnoise_destroy",
@@ -48,6 +50,8 @@ RNNOISE_SYMBOLS = [
 
 
 PCM_F32, PCM_I16, PCM_F32_UNIT = 0, 1, 2
+LINK_OFF, LINK_MAX, LINK_MIN = 0, 1, 2   # enum nnn_link_mode
+LINK_MODES = {"off": LINK_OFF, "max": LINK_MAX, "min": LINK_MIN}
 
 # per-stream state records (include/nnn_batch.h NNN_STREAM_STATE_*): byte offsets of the fields
 STREAM_STATE_BYTES = 11232
@@ -179,6 +183,10 @@ class Library:
             L.nnn_batch_set_gain_floor.argtypes = [vp, ip, i32, fp, i32]
             L.nnn_batch_get_gain_floor.argtypes = [vp, ip, i32, fp]
             L.nnn_batch_num_floored.argtypes = [vp]
+        for name in ("nnn_batch_set_channel_link", "nnn_node_set_channel_link"):
+            if hasattr(L, name):
+                getattr(L, name).argtypes = [vp, i32, i32]
+                getattr(L, name.replace("_set_", "_get_")).argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
         if hasattr(L, "nnn_node_set_gain_floor"):
             ip, fp = C.POINTER(i32), C.POINTER(C.c_float)
             L.nnn_node_set_gain_floor.argtypes = [vp, ip, i32, fp, i32]
@@ -278,3 +286,16 @@ def gain_floors(floors, n):
     if f.shape == (n, 22):
         return np.ascontiguousarray(f), 22
     raise ValueError(f"floors must be a scalar, [{n}] or [{n}, 22], got shape {f.shape}")
+
+
+def link_mode(mode):
+    """enum nnn_link_mode of "off" / "max" / "min" or of the number itself."""
+    if isinstance(mode, str):
+        if mode not in LINK_MODES:
+            raise ValueError(f"link mode must be one of {sorted(LINK_MODES)}, got {mode!r}")
+        return LINK_MODES[mode]
+    return int(mode)
+
+
+def link_mode_name(mode):
+    return {v: k for k, v in LINK_MODES.items()}[int(mode)]

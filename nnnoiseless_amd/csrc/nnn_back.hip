@@ -295,7 +295,7 @@ __device__ __forceinline__ void bk_gru_phase_b(const LayerDesc &L, const BkRnn &
 }
 
 // dense layer: neuron block w on wave w (its fragments and bias requested ahead by bk_dense_load); sink(row, neuron, value, q) with
-// row = 4 (lane >> 4) + q
+// row = 4 (lane >> 4) + q.  QUAD: the lane's four rows in one call, sink(4 (lane >> 4), neuron, values[4]) (as dense_layer's)
 __device__ __forceinline__ void bk_dense_load(const LayerDesc &L, const uint4 *__restrict__ Wq, const float *__restrict__ fpar, int nbi, int lane, BkW &w)
 {
     if (nbi >= L.nb) return;
@@ -303,7 +303,7 @@ __device__ __forceinline__ void bk_dense_load(const LayerDesc &L, const uint4 *_
     bk_frags_load(w.in, L.in, Wq + L.in.wofs + (size_t)nbi * L.in.ksteps * 64, lane);
     w.bias = neuron < L.n ? fpar[L.bias + neuron] : 0.0f;
 }
-template <class Sink>
+template <bool QUAD = false, class Sink>
 __device__ __forceinline__ void bk_dense(const LayerDesc &L, const BkRnn &R, const uint4 *__restrict__ Wq, const float *__restrict__ fpar, int wave,
                                          int lane, BkW &w, Sink &&sink)
 {
@@ -314,8 +314,15 @@ __device__ __forceinline__ void bk_dense(const LayerDesc &L, const BkRnn &R, con
         const uint4 *Bnb = Wq + L.in.wofs + (size_t)nbi * L.in.ksteps * 64;
         const f32x4 acc = bk_gemm(f32x4{w.bias, w.bias, w.bias, w.bias}, R.IN, R.in_ps, R.in_w, L.in, Bnb, lane, w.in);
         if (neuron < L.n) {
+            if constexpr (QUAD) {
+                float v[4];
 #pragma unroll
-            for (int q = 0; q < 4; q++) sink(4 * (lane >> 4) + q, neuron, activate(L.act, acc[q] * (1.0f / 256.0f), R.tab), q);
+                for (int q = 0; q < 4; q++) v[q] = activate(L.act, acc[q] * (1.0f / 256.0f), R.tab);
+                sink(4 * (lane >> 4), neuron, v);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; q++) sink(4 * (lane >> 4) + q, neuron, activate(L.act, acc[q] * (1.0f / 256.0f), R.tab), q);
+            }
         }
     }
 }
@@ -328,7 +335,10 @@ struct BkActs { int dense, vad, noise, dn, out, vo; };   // activation kinds of 
 // HELD: some stream of the batch is held (nnn_batch_hold_streams) -- the instantiation that looks at the live mask; the launch plan picks it.
 // FLOOR: some stream of the batch has a gain floor (nnn_batch_set_gain_floor) -- the instantiation that reads b.gfloor; the launch plan picks
 // it only while nnn_batch_num_floored() > 0, so that every other batch runs the code it ran before floors existed.
-template <bool FUSED, class SH, bool XR = false, bool HELD = false, bool FLOOR = false>
+// LINK: the batch links the channels of its stream groups (nnn_batch_set_channel_link) -- the instantiation whose gains sink takes a lane's
+// four rows of a band together (link_quad); the launch plan picks it only while a link is on, so that every other batch runs the code it
+// ran before links existed.
+template <bool FUSED, class SH, bool XR = false, bool HELD = false, bool FLOOR = false, bool LINK = false>
 __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0, BkActs acts, const uint4 *__restrict__ Wq,
                                               const float *__restrict__ fpar, int tile0, int g)
 {
@@ -500,7 +510,7 @@ __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0,
         NNN_STAMP(b, 10);
         // gains (ref: src/rnn.rs:378) and smoothing g = max(g, 0.6 lastg) (ref: src/denoise.rs:106-109), as rnn_gain_out with the prefetched
         // lastg; both also to `gout` for the synthesis
-        bk_dense(pl.out, R, Wq, fpar, wave, lane, W, [&](int lrow, int band, float v, int q) {
+        auto gain_out = [&](int lrow, int band, float v, int q) {
             const int row = r0 + lrow;
             const bool lv = live[lrow] != 0;
             if (FLOOR) v = fmaxf(v, q == 0 ? gfl[0] : (q == 1 ? gfl[1] : (q == 2 ? gfl[2] : gfl[3])));
@@ -515,7 +525,18 @@ __global__ void __launch_bounds__(BK_T) k_back(Buffers b, const StepParams *sp0,
             NNN_TIF(b, g, NB, f, tile, row)[(size_t)band * TILE] = gs;
             gout[lrow * BK_GW + band] = gr;
             gout[lrow * BK_GW + 24 + band] = gs;
-        });
+        };
+        if constexpr (LINK) {   // link first, then each row's own floor and smoothing
+            const unsigned long long lw = HELD ? live_word(b, tile) : ~0ull;
+            bk_dense<true>(pl.out, R, Wq, fpar, wave, lane, W, [&](int lrow, int band, const float (&v)[4]) {
+                float lk[4];
+                link_quad(b.link, live + lrow, (unsigned)(lw >> (r0 + lrow)) & 15u, v, lk);
+#pragma unroll
+                for (int q = 0; q < 4; q++) gain_out(lrow + q, band, lk[q], q);
+            });
+        } else {
+            bk_dense(pl.out, R, Wq, fpar, wave, lane, W, gain_out);
+        }
 #undef BK_EDGE
         if (!FUSED) {
             lds_barrier();   // (the next frame's features may be staged)

@@ -26,6 +26,7 @@ using namespace nnn;
 #include "nnn_batch_core.hip"
 #include "nnn_batch_streams.hip"
 #include "nnn_batch_floor.hip"
+#include "nnn_batch_link.hip"
 #include "nnn_batch_launch.hip"
 #include "nnn_batch_create.hip"
 #include "nnn_batch_snapshot.hip"

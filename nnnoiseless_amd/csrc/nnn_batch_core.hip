@@ -172,6 +172,8 @@ struct GroupPlan {
                                    // look at the live mask (and feed held streams zeros); otherwise the code a batch without a mask runs
     bool floor = false;            // some stream has a gain floor (nnn_batch_set_gain_floor): the back-end kernels in the instantiations that read the floor
                                    // rows; otherwise the code a batch without floors runs
+    bool link = false;             // the channels of the batch's stream groups are linked (nnn_batch_set_channel_link): the back-end kernels in the
+                                   // instantiations whose gains sink links; otherwise the code a batch without a link runs
     bool head = false;             // k_hp2 also runs the LPC sums' head (and k_pitch<true> takes it)
     bool lpc_in_pitch = false;     // k_pitch<true> does the LPC analysis
     int lpc_fc = 0;                // otherwise: k_lpc with lpc_fc frames per wave behind the high-pass, 0 = k_lpc_wide (lpc_launch)
@@ -300,6 +302,9 @@ struct nnn_batch {
     GrowBuf<char> fl_pin{nullptr, 0, MEM_PINNED};   // ... and their page-locked source
     hipEvent_t ev_fl = nullptr;        // the last copy out of fl_pin is done
     bool fl_busy = false;
+    // channel link (nnn_batch_set_channel_link): configuration, not state -- two integers of the host's, carried to
+    // the kernels in the argument blocks (Buffers::link), so a set is ordered with the launches by being made between them
+    int link_ch = 1, link_mode = 0;    // channels 1 / 2 / 4, NNN_LINK_OFF / MAX / MIN (off is kept as channels 1, mode NNN_LINK_OFF)
     // split calls (nnn_batch_analyze_* / nnn_batch_synthesize_*): frames analysed and not yet synthesised, the
     // scratch sets they lie in and the ring slot of the first one
     int pending = 0, pending_set0 = 0, pending_slot = 0;

@@ -71,6 +71,7 @@ static void plan_group(const nnn_batch *h, int g, GroupPlan &p)
     const bool split = k.hp_split >= 0 ? k.hp_split != 0 : h->NT <= 256;
     p.hp = !split ? 0 : ((k.hp_tpb ? k.hp_tpb == 2 : (g > 1 && h->NT >= 8)) ? 2 : 1);
     p.floor = h->n_floored > 0;   // (nnn_batch_set_gain_floor; the host's count is as the device's rows will be when the launch runs, like the mask's)
+    p.link = h->link_ch > 1;   // (nnn_batch_set_channel_link: the argument blocks carry the setting, Buffers::link)
     p.held = h->n_held > 0;   // (the host's copy of the mask is as the device's will be when the launch runs: hold and resume are enqueued in call order)
     // One-frame groups of batches whose pitch launch is a single round of workgroups (two 8-wave blocks per compute unit) run the LPC
     // analysis inside k_pitch: one launch fewer on the critical path of a real-time tick (measured per one-frame call: -6 us at 4096
@@ -99,27 +100,31 @@ static void plan_group(const nnn_batch *h, int g, GroupPlan &p)
 // 160 KB (raise_lds_limits): an instantiation cannot be launched without having had its limit raised.
 using RnnWfKernel = decltype(&k_rnn_wf<WfShapeAny>);
 using BackKernel = decltype(&k_back<true, BkShapeBuiltin>);
-static const auto kRnnKernel = &k_rnn;
+using RnnPlainKernel = decltype(&k_rnn<false>);
+static const RnnPlainKernel kRnnKernels[2] = {k_rnn<false>, k_rnn<true>};   // [channels linked]
 static const auto kVadKernel = &k_vad;
 static const auto kNetKernel = &k_net;   // (launched by nnn_batch_network_device, nnn_batch_network.hip)
 static const RnnWfKernel kRnnWfKernels[2] = {k_rnn_wf<WfShapeAny>, k_rnn_wf<BkShapeBuiltin>};   // [the model is of the built-in shape class]
-static const BackKernel kBackFused[2][2][2] = {   // [X rides in k_pitch][some stream held][some stream floored]
-    {{k_back<true, BkShapeBuiltin, false, false, false>, k_back<true, BkShapeBuiltin, false, false, true>},
-     {k_back<true, BkShapeBuiltin, false, true, false>, k_back<true, BkShapeBuiltin, false, true, true>}},
-    {{k_back<true, BkShapeBuiltin, true, false, false>, k_back<true, BkShapeBuiltin, true, false, true>},
-     {k_back<true, BkShapeBuiltin, true, true, false>, k_back<true, BkShapeBuiltin, true, true, true>}}};
-static const BackKernel kBackRnnAlone[2][2] = {   // [some stream held][some stream floored]
-    {k_back<false, BkShapeBuiltin, false, false, false>, k_back<false, BkShapeBuiltin, false, false, true>},
-    {k_back<false, BkShapeBuiltin, false, true, false>, k_back<false, BkShapeBuiltin, false, true, true>}};
+#define NNN_BK(F, XR, HELD, FLOOR) {k_back<F, BkShapeBuiltin, XR, HELD, FLOOR, false>, k_back<F, BkShapeBuiltin, XR, HELD, FLOOR, true>}
+static const BackKernel kBackFused[2][2][2][2] = {   // [X rides in k_pitch][some stream held][some stream floored][channels linked]
+    {{NNN_BK(true, false, false, false), NNN_BK(true, false, false, true)}, {NNN_BK(true, false, true, false), NNN_BK(true, false, true, true)}},
+    {{NNN_BK(true, true, false, false), NNN_BK(true, true, false, true)}, {NNN_BK(true, true, true, false), NNN_BK(true, true, true, true)}}};
+static const BackKernel kBackRnnAlone[2][2][2] = {   // [some stream held][some stream floored][channels linked]
+    {NNN_BK(false, false, false, false), NNN_BK(false, false, false, true)},
+    {NNN_BK(false, false, true, false), NNN_BK(false, false, true, true)}};
+#undef NNN_BK
 static std::vector<const void *> big_lds_kernels()
 {
-    std::vector<const void *> v{(const void *)kRnnKernel};
+    std::vector<const void *> v;
+    for (RnnPlainKernel k : kRnnKernels) v.push_back((const void *)k);
     for (RnnWfKernel k : kRnnWfKernels) v.push_back((const void *)k);
     for (const auto &by_held : kBackFused)
         for (const auto &by_floor : by_held)
-            for (BackKernel k : by_floor) v.push_back((const void *)k);
+            for (const auto &by_link : by_floor)
+                for (BackKernel k : by_link) v.push_back((const void *)k);
     for (const auto &by_floor : kBackRnnAlone)
-        for (BackKernel k : by_floor) v.push_back((const void *)k);
+        for (const auto &by_link : by_floor)
+            for (BackKernel k : by_link) v.push_back((const void *)k);
     v.push_back((const void *)kVadKernel);
     v.push_back((const void *)kNetKernel);
     return v;
@@ -162,7 +167,7 @@ static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, cons
     case ST_FFT:
         if (p.back == BACK_FUSED) {   // the fused back end takes the place of this stage and the two behind it: one launch per resident model
             for (const nnn_batch::ModelGroup &G : h->groups)   // (riders: its X transform done by k_pitch's rider blocks, see xt_rider)
-                L.go(K_BACK, kBackFused[p.riders][p.held][p.floor], dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.back_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
+                L.go(K_BACK, kBackFused[p.riders][p.held][p.floor][p.link], dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.back_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
             break;
         }
         L.go(K_FFT_XP, k_fft_xp, dim3(Sp * ug / FFT_SPB), dim3(64 * FFT_SPB), 0, b, sp0, g);
@@ -172,12 +177,12 @@ static void launch_stage(nnn_batch *h, int s, int set0, const GroupPlan &p, cons
         for (size_t i = 0; i < h->groups.size(); i++) {   // one launch per resident model (a run of whole tiles)
             const nnn_batch::ModelGroup &G = h->groups[i];
             if (p.rnn[i] == RK_BACK)
-                L.go(K_RNN, kBackRnnAlone[p.held][p.floor], dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.rnn16_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
+                L.go(K_RNN, kBackRnnAlone[p.held][p.floor][p.link], dim3((unsigned)(G.ntiles * (TILE / BK_ROWS))), dim3(BK_T), G.rnn16_lds, b, sp0, G.acts, G.wq, G.fpar, G.tile0, g);
             else if (p.rnn[i] == RK_WF_BUILTIN || p.rnn[i] == RK_WF_ANY)
                 L.go(K_RNN, kRnnWfKernels[p.rnn[i] == RK_WF_BUILTIN], dim3((unsigned)(G.ntiles * (TILE / WF_ROWS))), dim3(64 * WF_WAVES), G.wf_lds, b, G.plan, G.wp,
                      G.wq, G.fpar, G.tile0, g);
             else
-                L.go(K_RNN, kRnnKernel, dim3((unsigned)(G.ntiles * (TILE / G.rows))), dim3(64 * RNN_WAVES), G.rnn_lds, b, G.plan, G.wq, G.fpar,
+                L.go(K_RNN, kRnnKernels[p.link], dim3((unsigned)(G.ntiles * (TILE / G.rows))), dim3(64 * RNN_WAVES), G.rnn_lds, b, G.plan, G.wq, G.fpar,
                      G.tile0, G.rows, g);
         }
         break;

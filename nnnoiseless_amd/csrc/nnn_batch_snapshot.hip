@@ -1,6 +1,6 @@
 // nnn_batch_snapshot.hip -- whole-batch state images (state_bytes, save_state, load_state) and clone.
-// Needs nnn_batch_core.hip (quiesce), create_batch of nnn_batch_create.hip, hold_prepare of nnn_batch_streams.hip and floor_clone of
-// nnn_batch_floor.hip.
+// Needs nnn_batch_core.hip (quiesce), create_batch of nnn_batch_create.hip, hold_prepare of nnn_batch_streams.hip, floor_clone of
+// nnn_batch_floor.hip and link_clone of nnn_batch_link.hip.
 #pragma once
 
 // ---- state snapshots: DenoiseState is Clone in the reference (src/denoise.rs:36) ------------------------------------
@@ -99,6 +99,7 @@ extern "C" nnn_batch *nnn_batch_clone(nnn_batch *h)
         fail("copy of the gain floors failed");
         return nullptr;
     }
+    link_clone(c, h);   // ... and the same channel link
     c->frame_count = h->frame_count;
     c->group_count = h->group_count;
     c->paths = h->paths;

@@ -213,6 +213,9 @@ struct Buffers {
     const unsigned long long *live;   // [NT] one word per tile, bit i = stream i of the tile takes part in processing calls (cleared by
                              //      nnn_batch_hold_streams, set again by nnn_batch_resume_streams; padding streams: 0).  Null -- a batch
                              //      that never held a stream, the training rows -- means every stream is live.  Constant for a whole call.
+    int link;                // channel link (nnn_batch_set_channel_link): 0 = off; 2 or 4 = the streams of s / link share one gain per band, the
+                             //      largest of their network outputs (NNN_LINK_MAX); -2 or -4 = the smallest (NNN_LINK_MIN).  Configuration, not
+                             //      state.  Constant for a whole call.
 };
 
 // The live mask.  A block asks once, with a block-uniform tile: one word, a uniform branch.

@@ -476,3 +476,21 @@ extern "C" int nnn_node_num_floored(const nnn_node *n)
         for (const auto &s : n->shards) total += nnn_batch_num_floored(s.b);
     return total;
 }
+
+// channel link of every shard (nnn_batch_set_channel_link): every shard is checked -- its own refusals, and a first stream that would split a
+// link group over two shards -- before any shard is changed
+int nnn_batch_check_channel_link(const nnn_batch *h, int channels, int mode, int first);   // nnn_batch_link.hip
+extern "C" int nnn_node_set_channel_link(nnn_node *n, int channels, int mode)
+{
+    if (!n) return nnn_set_error("null node");
+    for (const auto &s : n->shards)
+        if (int rc = nnn_batch_check_channel_link(s.b, channels, mode, s.lo)) return rc;
+    for (const auto &s : n->shards)
+        if (int rc = nnn_batch_set_channel_link(s.b, channels, mode)) return rc;
+    return 0;
+}
+extern "C" int nnn_node_get_channel_link(const nnn_node *n, int *channels, int *mode)
+{
+    if (!n || n->shards.empty()) return nnn_set_error("null node");
+    return nnn_batch_get_channel_link(n->shards[0].b, channels, mode);
+}

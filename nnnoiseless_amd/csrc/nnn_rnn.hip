@@ -188,6 +188,38 @@ __device__ __forceinline__ void rnn_gain_out(const Buffers &b, int f, int tile, 
     NNN_TIF(b, g, NB, f, tile, row)[(size_t)band * TILE] = gs;
 }
 
+// Channel link (nnn_batch_set_channel_link; `link` is Buffers::link, not 0): the network's gains `v` of one band for the four rows 4 k ..
+// 4 k + 3 of a tile -- what a lane of the output layer's 16x16 accumulator holds -- become one common gain per link group.  Rows are batch
+// indices modulo 4 (tiles and blocks start at multiples of 16), so the pairs (0, 1) and (2, 3) are the 2-channel groups and the four rows
+// the 4-channel group.  A row takes part while its frame is not silent (`nonsilent`, the kernel's per-row flags) and its stream is live
+// (bit q of `live4`); a row that does not keeps its own value and gives none, and a group with one member left keeps that member's value.
+// Max and min of finite values are exact and order-free: the host's max / min over the same members gives the same bits.
+__device__ __forceinline__ void link_quad(int link, const int *nonsilent, unsigned live4, const float (&v)[4], float (&out)[4])
+{
+    const bool mn = link < 0;
+    const float idle = mn ? INFINITY : -INFINITY;
+    bool m[4];
+    float x[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        m[q] = nonsilent[q] != 0 && ((live4 >> q) & 1u) != 0u;
+        x[q] = m[q] ? v[q] : idle;
+    }
+    const float p01 = mn ? fminf(x[0], x[1]) : fmaxf(x[0], x[1]), p23 = mn ? fminf(x[2], x[3]) : fmaxf(x[2], x[3]);
+    const float all = mn ? fminf(p01, p23) : fmaxf(p01, p23);
+    const bool four = link == 4 || link == -4;
+#pragma unroll
+    for (int q = 0; q < 4; q++) out[q] = m[q] ? (four ? all : (q < 2 ? p01 : p23)) : v[q];
+}
+// rnn_gain_out for the four rows row0 .. row0 + 3 (row0 a multiple of 4) of a linked batch: link first, then each stream's own floor
+__device__ __forceinline__ void rnn_gain_out4(const Buffers &b, int f, int tile, int row0, int band, const int *nonsilent, const float (&v)[4])
+{
+    float lk[4];
+    link_quad(b.link, nonsilent, (unsigned)(live_word(b, tile) >> row0) & 15u, v, lk);
+#pragma unroll
+    for (int q = 0; q < 4; q++) rnn_gain_out(b, f, tile, row0 + q, band, nonsilent[q] != 0, lk[q]);
+}
+
 struct RnnLds {
     const float *tab;
     int *live;            // rows whose frame is not silent (this frame)
@@ -284,8 +316,9 @@ __device__ __forceinline__ void gru_layer(const Buffers &b, const LayerDesc &L, 
 }
 
 // dense layer on the matrix cores: act(W x + b) for every (neuron block, 16-stream block) unit, units dealt round-robin to
-// the block's waves (a layer wider than the waves are many takes several rounds); `sink(row, neuron, value)` per output
-template <class Sink>
+// the block's waves (a layer wider than the waves are many takes several rounds); `sink(row, neuron, value)` per output.  QUAD: the four
+// rows a lane holds of its neuron in one call, `sink(first row, neuron, values[4])` (the channel link's form of the gains sink, link_quad)
+template <bool QUAD = false, class Sink>
 __device__ __forceinline__ void dense_layer(const LayerDesc &L, const RnnPlan &pl, const RnnLds &lds, const uint4 *__restrict__ Wq,
                                             const float *__restrict__ fpar, int wave, int lane, Sink &&sink)
 {
@@ -301,9 +334,16 @@ __device__ __forceinline__ void dense_layer(const LayerDesc &L, const RnnPlan &p
         acc[0][0] = f32x4{bv, bv, bv, bv};
         gemm_acc<1, 1, 0>(acc, lds.IN, lds.in_ps, pl.in_w, mb0, L.in, Bnb, lane, fr);
         if (neuron < L.n) {
+            if constexpr (QUAD) {
+                float v[4];
 #pragma unroll
-            for (int q = 0; q < 4; q++)
-                sink(mb0 * 16 + 4 * (lane >> 4) + q, neuron, activate(L.act, acc[0][0][q] * (1.0f / 256.0f), lds.tab));
+                for (int q = 0; q < 4; q++) v[q] = activate(L.act, acc[0][0][q] * (1.0f / 256.0f), lds.tab);
+                sink(mb0 * 16 + 4 * (lane >> 4), neuron, v);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; q++)
+                    sink(mb0 * 16 + 4 * (lane >> 4) + q, neuron, activate(L.act, acc[0][0][q] * (1.0f / 256.0f), lds.tab));
+            }
         }
     }
 }
@@ -409,6 +449,11 @@ __host__ __device__ constexpr RnnLdsAt rnn_lds(const RnnPlan &pl, int rows)
 }
 static_assert(rnn_lds(BkShapeBuiltin::plan(), 16).total == 66816 && rnn_lds(BkShapeBuiltin::plan(), 32).total == 132096, "k_rnn's LDS for the built-in shape class");
 
+// LINK: the batch links the channels of its stream groups (nnn_batch_set_channel_link) -- the instantiation whose gains sink takes a lane's
+// four rows of a band together (rnn_gain_out4); the launch plan picks it only while a link is on.  A template flag as in k_back, not a
+// run-time test of b.link as in k_rnn_wf: this kernel keeps some five hundred scalars in vector lanes, and a run-time test -- around the
+// whole sink, around link_quad alone, or carried in the rows' LDS flags -- moved its register allocation from 203 to 205 - 209 registers.
+template <bool LINK = false>
 __global__ void __launch_bounds__(64 * RNN_WAVES) k_rnn(Buffers b, RnnPlan pl, const uint4 *__restrict__ Wq,
                                                           const float *__restrict__ fpar, int tile0, int rm, int g)
 {
@@ -526,8 +571,12 @@ __global__ void __launch_bounds__(64 * RNN_WAVES) k_rnn(Buffers b, RnnPlan pl, c
         NNN_MB(mb_dn, NNN_GRU_DN)                                           // ref: src/rnn.rs:368-377
         NNN_STAMP(b, 14);
         // gains and their smoothing
-        dense_layer(pl.out, pl, lds, Wq, fpar, wave, lane,
-                    [&](int lrow, int band, float v) { rnn_gain_out(b, f, tile, r0 + lrow, band, live[lrow] != 0, v); });
+        if constexpr (LINK)
+            dense_layer<true>(pl.out, pl, lds, Wq, fpar, wave, lane,
+                              [&](int lrow, int band, const float (&v)[4]) { rnn_gain_out4(b, f, tile, r0 + lrow, band, live + lrow, v); });
+        else
+            dense_layer(pl.out, pl, lds, Wq, fpar, wave, lane,
+                        [&](int lrow, int band, float v) { rnn_gain_out(b, f, tile, r0 + lrow, band, live[lrow] != 0, v); });
         feat_next();   // layer shapes that keep every wave busy: the next frame's features go last
         NNN_STAMP(b, 15);
     }

@@ -236,7 +236,7 @@ __device__ __forceinline__ void wf_dense_load(WfDenseW<KS> &w, const LayerDesc &
     const int neuron = nbi * 16 + (lane & 15);
     w.bias = neuron < L.n ? fpar[L.bias + neuron] : 0.0f;
 }
-template <int KS, class Sink>
+template <bool QUAD = false, int KS, class Sink>   // (QUAD: as dense_layer's)
 __device__ __forceinline__ void wf_dense(const LayerDesc &L, const unsigned short *Ain, int in_w, const uint4 *__restrict__ Wq, const WfDenseW<KS> &w,
                                          const float *tab, int nbi, int lane, Sink &&sink)
 {
@@ -246,8 +246,15 @@ __device__ __forceinline__ void wf_dense(const LayerDesc &L, const unsigned shor
     acc[0][0] = f32x4{w.bias, w.bias, w.bias, w.bias};
     gemm_acc<1, 1, 0, KS>(acc, Ain, WF_ROWS * in_w, in_w, 0, L.in, Bnb, lane, w.fr);
     if (neuron < L.n) {
+        if constexpr (QUAD) {
+            float v[4];
 #pragma unroll
-        for (int q = 0; q < 4; q++) sink(4 * (lane >> 4) + q, neuron, activate(L.act, acc[0][0][q] * (1.0f / 256.0f), tab));
+            for (int q = 0; q < 4; q++) v[q] = activate(L.act, acc[0][0][q] * (1.0f / 256.0f), tab);
+            sink(4 * (lane >> 4), neuron, v);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; q++) sink(4 * (lane >> 4) + q, neuron, activate(L.act, acc[0][0][q] * (1.0f / 256.0f), tab));
+        }
     }
 }
 
@@ -407,8 +414,14 @@ __global__ void __launch_bounds__(64 * WF_WAVES, NNN_WF_MINWAVES) k_rnn_wf(Buffe
             if (mine_o) {   // gains of frame fo and their smoothing
                 const int *lv = live + 16 * (fo & 7);
                 wf_dense_load(dw, pl.out, Wq, fpar, wave - W_V, lane);
-                wf_dense(pl.out, SPdn, wp.sw_dn, Wq, dw, tab, wave - W_V, lane,
-                         [&](int lrow, int band, float v) { rnn_gain_out(b, fo, tile, r0 + lrow, band, lv[lrow] != 0, v); });
+                wf_dense<true>(pl.out, SPdn, wp.sw_dn, Wq, dw, tab, wave - W_V, lane, [&](int lrow, int band, const float (&v)[4]) {
+                    if (b.link) {   // (nnn_batch_set_channel_link: one gain per band for the channels of a link group)
+                        rnn_gain_out4(b, fo, tile, r0 + lrow, band, lv + lrow, v);
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < 4; q++) rnn_gain_out(b, fo, tile, r0 + lrow + q, band, lv[lrow + q] != 0, v[q]);
+                    }
+                });
             }
         } else {
             if (on_f) wf_features(b, wf_features_in(wts), ff, tile, r0, lane, crs, dc, cnb, FS, live + 16 * (ff & 7), mem_id);

@@ -128,6 +128,16 @@ class NodeDenoiser:
     def num_floored(self):
         return int(self._lib.L.nnn_node_num_floored(self._h))
 
+    def set_channel_link(self, channels, mode="max"):
+        """Channel link of every shard (BatchDenoiser.set_channel_link); refused if a shard's first stream is not a multiple of `channels`."""
+        self._lib.check(self._lib.L.nnn_node_set_channel_link(self._h, int(channels), _ffi.link_mode(mode)))
+
+    def channel_link(self):
+        """(channels, mode) of the node's shards: (1, "off") while off."""
+        ch, md = C.c_int32(0), C.c_int32(0)
+        self._lib.check(self._lib.L.nnn_node_get_channel_link(self._h, C.byref(ch), C.byref(md)))
+        return ch.value, _ffi.link_mode_name(md.value)
+
     def export_streams(self, idx):
         """Portable records of node-global streams, uint8 [len(idx), STREAM_STATE_BYTES] (BatchDenoiser.export_streams)."""
         a, p = _ffi.stream_list(idx)
