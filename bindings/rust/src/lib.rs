@@ -1,7 +1,7 @@
 //! Drop-in façade with the reference's API (`DenoiseState`, `RnnModel`, jneem/nnnoiseless src/denoise.rs,
 //! src/rnn.rs) over the MI355X backend's C ABI (include/nnn_batch.h).  Written against the FFI only;
 //! it was not compiled in the build image, which has no Rust toolchain.
-use std::os::raw::{c_float, c_int, c_void};
+use std::os::raw::{c_float, c_int, c_long, c_void};
 
 #[repr(C)]
 pub struct RawModel {
@@ -13,6 +13,10 @@ pub struct RawBatch {
 }
 #[repr(C)]
 pub struct RawNode {
+    _p: [u8; 0],
+}
+#[repr(C)]
+pub struct RawRate {
     _p: [u8; 0],
 }
 
@@ -121,6 +125,41 @@ extern "C" {
         vad: *mut c_float,
         n_frames: c_int,
         layout: *const PcmLayout,
+    ) -> c_int;
+    // include/nnn_rate.h
+    fn nnn_rate_create(b: *mut RawBatch, source_rate: f64, max_in: c_long) -> *mut RawRate;
+    fn nnn_rate_destroy(a: *mut RawRate);
+    fn nnn_rate_reset(a: *mut RawRate) -> c_int;
+    fn nnn_rate_reset_streams(a: *mut RawRate, streams: *const c_int, n: c_int) -> c_int;
+    fn nnn_rate_max_output(a: *const RawRate, n_in: c_long) -> c_long;
+    fn nnn_rate_max_frames(a: *const RawRate, n_in: c_long) -> c_int;
+    fn nnn_rate_carried(a: *const RawRate) -> c_long;
+    fn nnn_rate_process_device(
+        a: *mut RawRate,
+        d_in: *const c_void,
+        n_in: c_long,
+        in_stride: usize,
+        d_out: *mut c_void,
+        cap_out: c_long,
+        out_stride: usize,
+        n_out: *mut c_long,
+        d_vad: *mut c_float,
+        cap_frames: c_int,
+        n_frames: *mut c_int,
+        format: c_int,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    fn nnn_rate_process_host(
+        a: *mut RawRate,
+        input: *const c_void,
+        n_in: c_long,
+        output: *mut c_void,
+        cap_out: c_long,
+        n_out: *mut c_long,
+        vad: *mut c_float,
+        cap_frames: c_int,
+        n_frames: *mut c_int,
+        format: c_int,
     ) -> c_int;
 }
 
@@ -386,6 +425,108 @@ impl Clone for BatchDenoiser {
 impl Drop for BatchDenoiser {
     fn drop(&mut self) {
         unsafe { nnn_batch_destroy(self.raw) }
+    }
+}
+
+/// Streams at another sample rate in and out of a 48 kHz batch (include/nnn_rate.h): the CLI's resampler (src/nnnoiseless.rs:106-131,
+/// :179-227) in front of the batch's ordinary call and the same interpolator at the inverse ratio behind it, in one asynchronous call on
+/// the GPU.  The adapter carries the partial frame and both legs' histories; any chunking gives the same bits.  It borrows the batch
+/// for its lifetime and drives it: reach the batch through `batch()` to reset, hold or resume streams.
+pub struct RateAdapter<'b> {
+    raw: *mut RawRate,
+    batch: &'b mut BatchDenoiser,
+}
+unsafe impl<'b> Send for RateAdapter<'b> {}
+
+impl<'b> RateAdapter<'b> {
+    /// `None` where the backend refuses: a rate of 0 or 48000 (use the batch), `max_in` of 0.
+    pub fn new(batch: &'b mut BatchDenoiser, source_rate: f64, max_in: usize) -> Option<RateAdapter<'b>> {
+        let raw = unsafe { nnn_rate_create(batch.raw, source_rate, max_in as c_long) };
+        if raw.is_null() {
+            None
+        } else {
+            Some(RateAdapter { raw, batch })
+        }
+    }
+    pub fn batch(&mut self) -> &mut BatchDenoiser {
+        self.batch
+    }
+    /// Bound of the source-rate samples a call of `n_in` samples per stream can return.
+    pub fn max_output(&self, n_in: usize) -> usize {
+        unsafe { nnn_rate_max_output(self.raw, n_in as c_long) as usize }
+    }
+    /// Bound of the frames (VAD rows) such a call can complete.
+    pub fn max_frames(&self, n_in: usize) -> usize {
+        unsafe { nnn_rate_max_frames(self.raw, n_in as c_long) as usize }
+    }
+    /// 48 kHz samples of the partial frame now held.
+    pub fn carried(&self) -> usize {
+        unsafe { nnn_rate_carried(self.raw) as usize }
+    }
+    /// `input`: `[n_streams][n_in]` floats in i16 range; `output`: `[n_streams][cap_out]`, `cap_out >= max_output(n_in)`; `vad`:
+    /// `[cap_frames][n_streams]`, `cap_frames >= max_frames(n_in)`.  Returns `(n_out, n_frames)`; `Err` (nothing consumed) where the
+    /// backend refuses the call.
+    pub fn process(&mut self, input: &[f32], n_in: usize, output: &mut [f32], vad: &mut [f32]) -> Result<(usize, usize), ()> {
+        let s = self.batch.n;
+        if s == 0 || input.len() != s * n_in || output.len() % s != 0 || vad.len() % s != 0 {
+            return Err(());
+        }
+        let (mut n_out, mut n_frames): (c_long, c_int) = (0, 0);
+        let rc = unsafe {
+            nnn_rate_process_host(
+                self.raw,
+                input.as_ptr() as *const c_void,
+                n_in as c_long,
+                output.as_mut_ptr() as *mut c_void,
+                (output.len() / s) as c_long,
+                &mut n_out,
+                vad.as_mut_ptr(),
+                (vad.len() / s) as c_int,
+                &mut n_frames,
+                0,
+            )
+        };
+        if rc == 0 { Ok((n_out as usize, n_frames as usize)) } else { Err(()) }
+    }
+    /// Raw device pointers, strides in elements of `format` (0 = f32 in i16 range, 1 = i16); asynchronous on `hip_stream` (null = the
+    /// batch's own stream).
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the batch's device with room for the strides and capacities given.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn process_device(
+        &mut self,
+        d_in: *const c_void,
+        n_in: usize,
+        in_stride: usize,
+        d_out: *mut c_void,
+        cap_out: usize,
+        out_stride: usize,
+        d_vad: *mut c_float,
+        cap_frames: usize,
+        format: c_int,
+        hip_stream: *mut c_void,
+    ) -> Result<(usize, usize), ()> {
+        let (mut n_out, mut n_frames): (c_long, c_int) = (0, 0);
+        let rc = nnn_rate_process_device(
+            self.raw, d_in, n_in as c_long, in_stride, d_out, cap_out as c_long, out_stride, &mut n_out, d_vad, cap_frames as c_int, &mut n_frames, format,
+            hip_stream,
+        );
+        if rc == 0 { Ok((n_out as usize, n_frames as usize)) } else { Err(()) }
+    }
+    /// The adapter alone back to its fresh state.
+    pub fn reset(&mut self) {
+        unsafe { nnn_rate_reset(self.raw) };
+    }
+    /// The listed streams' histories and carried samples cleared from the next call on (beside the batch's own `reset_streams`).
+    pub fn reset_streams(&mut self, streams: &[i32]) -> Result<(), ()> {
+        let rc = unsafe { nnn_rate_reset_streams(self.raw, streams.as_ptr(), streams.len() as c_int) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+}
+impl<'b> Drop for RateAdapter<'b> {
+    fn drop(&mut self) {
+        unsafe { nnn_rate_destroy(self.raw) }
     }
 }
 

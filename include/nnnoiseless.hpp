@@ -26,6 +26,7 @@
 
 #include "nnn_batch.h"
 #include "nnn_node.h"
+#include "nnn_rate.h"
 #include "nnn_resample.h"
 #include "nnn_train.h"
 
@@ -347,6 +348,49 @@ class Resampler {
 
   private:
     std::shared_ptr<nnn_resampler> r_;
+};
+
+// Streams at another sample rate in and out of a 48 kHz batch (include/nnn_rate.h): the CLI's resampler in front of the batch's ordinary
+// call and the same interpolator at the inverse ratio behind it, one asynchronous call; the adapter carries the partial frame and
+// both legs' histories.  It borrows the batch, which must outlive it.
+class RateAdapter {
+  public:
+    RateAdapter(BatchDenoiser &batch, double source_rate, long max_in) : a_(nnn_rate_create(batch.raw(), source_rate, max_in), nnn_rate_destroy)
+    {
+        if (!a_) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    long max_output(long n_in) const { return nnn_rate_max_output(a_.get(), n_in); }
+    int max_frames(long n_in) const { return nnn_rate_max_frames(a_.get(), n_in); }
+    long carried() const { return nnn_rate_carried(a_.get()); }
+    struct Counts {
+        long n_out;     // source-rate samples per stream the call returned
+        int n_frames;   // frames (VAD rows) it completed
+    };
+    // host buffers, dense [n_streams][n_in] -> [n_streams][cap_out], vad [cap_frames][n_streams] (may be null); format NNN_PCM_F32 or NNN_PCM_I16
+    Counts process(const void *in, long n_in, void *out, long cap_out, float *vad, int cap_frames, int format = NNN_PCM_F32)
+    {
+        Counts c = {0, 0};
+        check(nnn_rate_process_host(a_.get(), in, n_in, out, cap_out, &c.n_out, vad, cap_frames, &c.n_frames, format));
+        return c;
+    }
+    // device buffers, strides in elements of the format; asynchronous on hip_stream (nullptr = the batch's own stream)
+    Counts process_device(const void *d_in, long n_in, size_t in_stride, void *d_out, long cap_out, size_t out_stride, float *d_vad, int cap_frames,
+                          int format = NNN_PCM_F32, void *hip_stream = nullptr)
+    {
+        Counts c = {0, 0};
+        check(nnn_rate_process_device(a_.get(), d_in, n_in, in_stride, d_out, cap_out, out_stride, &c.n_out, d_vad, cap_frames, &c.n_frames, format, hip_stream));
+        return c;
+    }
+    void reset() { check(nnn_rate_reset(a_.get())); }
+    // beside BatchDenoiser::reset_streams: the listed streams' histories and carried samples cleared from the next call on
+    void reset_streams(const std::vector<int> &streams) { check(nnn_rate_reset_streams(a_.get(), streams.data(), (int)streams.size())); }
+
+  private:
+    static void check(int rc)
+    {
+        if (rc) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    std::shared_ptr<nnn_rate> a_;
 };
 
 

@@ -35,6 +35,11 @@ RESAMPLE_SYMBOLS = [
     "nnn_resampler_create", "nnn_resampler_destroy", "nnn_resampler_reset", "nnn_resampler_max_output",
     "nnn_resampler_process_device", "nnn_resampler_process_host",
 ]
+# include/nnn_rate.h (the rate adapter; a list of its own: the adapter is an object beside the batch, not part of it)
+RATE_SYMBOLS = [
+    "nnn_rate_create", "nnn_rate_destroy", "nnn_rate_reset", "nnn_rate_reset_streams", "nnn_rate_max_output", "nnn_rate_max_frames",
+    "nnn_rate_carried", "nnn_rate_process_device", "nnn_rate_process_host", "nnn_rate_debug_tables",
+]
 NODE_SYMBOLS = [
     "nnn_node_create", "nnn_node_destroy", "nnn_node_num_streams", "nnn_node_num_shards", "nnn_node_shard", "nnn_node_batch", "nnn_node_reset",
     "nnn_node_process_host", "nnn_node_process_pcm_host", "nnn_node_process_device", "nnn_node_process_device_streams", "nnn_node_synchronize",
@@ -234,6 +239,22 @@ class Library:
         L.nnn_resampler_max_output.argtypes = [vp, C.c_long]
         L.nnn_resampler_process_device.argtypes = [vp, vp, C.c_long, sz, vp, C.c_long, sz, C.POINTER(C.c_long), vp]
         L.nnn_resampler_process_host.argtypes = [vp, vp, C.c_long, vp, C.c_long, C.POINTER(C.c_long)]
+        if hasattr(L, "nnn_rate_create"):
+            lp = C.POINTER(C.c_long)
+            L.nnn_rate_create.restype = vp
+            L.nnn_rate_create.argtypes = [vp, C.c_double, C.c_long]
+            L.nnn_rate_destroy.restype = None
+            L.nnn_rate_destroy.argtypes = [vp]
+            L.nnn_rate_reset.argtypes = [vp]
+            L.nnn_rate_reset_streams.argtypes = [vp, C.POINTER(i32), i32]
+            L.nnn_rate_max_output.restype = C.c_long
+            L.nnn_rate_max_output.argtypes = [vp, C.c_long]
+            L.nnn_rate_max_frames.argtypes = [vp, C.c_long]
+            L.nnn_rate_carried.restype = C.c_long
+            L.nnn_rate_carried.argtypes = [vp]
+            L.nnn_rate_process_device.argtypes = [vp, vp, C.c_long, sz, vp, C.c_long, sz, lp, vp, i32, C.POINTER(i32), i32, vp]
+            L.nnn_rate_process_host.argtypes = [vp, vp, C.c_long, vp, C.c_long, lp, vp, i32, C.POINTER(i32), i32]
+            L.nnn_rate_debug_tables.argtypes = [vp, lp, C.POINTER(C.c_double)]
         L.nnn_last_error.restype = C.c_char_p
         L.rnnoise_create.restype = vp
         L.rnnoise_create.argtypes = [vp]

@@ -35,4 +35,5 @@ using namespace nnn;
 #include "nnn_batch_vad.hip"
 #include "nnn_batch_network.hip"
 #include "nnn_batch_debug.hip"
+#include "nnn_rate.hip"
 #include "nnn_train.hip"

@@ -10,31 +10,12 @@
 #include <vector>
 
 #include "../../include/nnn_resample.h"
+#include "nnn_rs_sched.h"   // the schedule, the weights and the fold, shared with the rate adapter
 
 extern "C" const char *nnn_last_error(void);
 int nnn_set_error(const char *msg);   // nnn_batch_core.hip
 
 namespace {
-
-constexpr int RS_TAPS = 16, RS_DEPTH = RS_TAPS / 2;
-
-// One output sample: the fold of Sinc::interpolate.  `e` points at the ring as it stands (frames[i] = e[i], i < 16, oldest first);
-// w[2 n] / w[2 n + 1] = the left / right tap weight of step n (f64), nd = max_depth, idx = the interpolator's idx.
-__device__ __forceinline__ float sinc_fold(const float *e, const double *w, int nd, int idx)
-{
-    float v = 0.0f;
-    for (int n = 0; n < nd; n++) {
-        v += (float)(w[2 * n] * (double)e[(idx - n) & (RS_TAPS - 1)]);          // frames[nl - n]
-        v += (float)(w[2 * n + 1] * (double)e[(idx + 1 + n) & (RS_TAPS - 1)]);  // frames[nr + n] (the ring index wraps)
-    }
-    return v;
-}
-
-struct RsOut {   // per output sample of a call, shared by all streams
-    int consumed;   // source samples of this call pushed before it
-    int idx, nd;    // interpolator idx and max_depth at that point
-    int pad;
-};
 
 __global__ void k_resample(const float *in, size_t in_stride, const float *hist, float *out, size_t out_stride, const RsOut *sched,
                            const double *w, int n_out, int n_streams)
@@ -123,7 +104,7 @@ extern "C" int nnn_resampler_reset(nnn_resampler *r)
 
 extern "C" long nnn_resampler_max_output(const nnn_resampler *r, long n_in)
 {
-    return r ? (long)ceil(((double)n_in + 2.0) / r->ratio) + 2 : 0;
+    return r ? rs_max_output(r->ratio, n_in) : 0;
 }
 
 extern "C" int nnn_resampler_process_device(nnn_resampler *r, const float *d_in, long n_in, size_t in_stride, float *d_out,
@@ -140,35 +121,12 @@ extern "C" int nnn_resampler_process_device(nnn_resampler *r, const float *d_in,
     // ---- the position sequence of Resample::next_sample (src/nnnoiseless.rs:107-120) and the weights of Sinc::interpolate
     std::vector<RsOut> sched;
     std::vector<double> w;
-    const double pi = 3.14159265358979323846;
-    double pos = r->pos;
-    int idx = r->idx;
-    long consumed = 0, credit = r->credit;
-    while ((long)sched.size() < cap_out) {
-        double p = pos + r->ratio;
-        long need = 0;
-        while (p >= 1.0) { p -= 1.0; need++; }
-        const long need_now = need - credit;    // `credit` of them went into the ring with an earlier call
-        if (consumed + need_now > n_in) break;  // this output waits for the next call's samples
-        pos = p;
-        consumed += need_now;
-        credit = 0;
-        for (long k = 0; k < need_now && idx < RS_DEPTH; k++) idx++;   // Sinc::next_source_frame
-        const int nl = idx, nr = idx + 1, rightmost = nl + RS_DEPTH, leftmost = nr - RS_DEPTH;
-        const int nd = rightmost >= RS_TAPS ? RS_TAPS - RS_DEPTH : (leftmost < 0 ? RS_DEPTH + leftmost : RS_DEPTH);
-        RsOut o{(int)consumed, idx, nd, 0};
+    RsPos after;
+    after.pos = r->pos, after.idx = r->idx, after.credit = r->credit;
+    rs_schedule(r->ratio, after, n_in, cap_out, [&](const RsOut &o, const double *ow) {
         sched.push_back(o);
-        const double phil = pos, phir = 1.0 - pos;
-        for (int n = 0; n < RS_DEPTH; n++) {
-            double a = pi * (phil + (double)n);
-            double first = a == 0.0 ? 1.0 : sin(a) / a, second = 0.5 + 0.5 * cos(a / (double)RS_DEPTH);
-            w.push_back(first * second);
-            a = pi * (phir + (double)n);
-            first = a == 0.0 ? 1.0 : sin(a) / a;
-            second = 0.5 + 0.5 * cos(a / (double)RS_DEPTH);
-            w.push_back(first * second);
-        }
-    }
+        w.insert(w.end(), ow, ow + RS_TAPS);
+    });
     const long n = (long)sched.size();
     if (n > r->cap) {
         hipStreamSynchronize(st);
@@ -188,21 +146,14 @@ extern "C" int nnn_resampler_process_device(nnn_resampler *r, const float *d_in,
         hipLaunchKernelGGL(k_resample, dim3((unsigned)((n + 255) / 256), (unsigned)r->n_streams), dim3(256), 0, st, d_in, in_stride,
                            (const float *)r->hist, d_out, out_stride, (const RsOut *)r->sched, (const double *)r->w, (int)n, r->n_streams);
     }
-    // Source samples of this call beyond those its completed outputs pulled belong to the next output, whose other samples have
-    // not arrived.  The reference pulls a sample only inside the loop of the output that needs it; pushing these now is the same
-    // thing (a push only moves the ring, and the ring is looked at when that output is interpolated): they are counted as
-    // `credit` against that output's need, and the position keeps its value.
+    // (source samples beyond those the completed outputs pulled: rs_schedule counts them as credit)
     if (n_in > 0)
         hipLaunchKernelGGL(k_resample_hist, dim3((unsigned)((r->n_streams * RS_TAPS + 255) / 256)), dim3(256), 0, st, d_in, in_stride, r->hist,
                            n_in, r->n_streams);
     if (hipGetLastError() != hipSuccess) return rfail("resampler: launch failed");
-    {
-        const long early = n_in - consumed;
-        for (long k = 0; k < early && idx < RS_DEPTH; k++) idx++;
-        r->credit = credit + early;
-        r->pos = pos;
-        r->idx = idx;
-    }
+    r->pos = after.pos;
+    r->idx = after.idx;
+    r->credit = after.credit;
     *n_out = n;
     return 0;
 }

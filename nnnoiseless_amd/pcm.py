@@ -124,3 +124,94 @@ class Resampler:
             self._h = None
 
     __del__ = close
+
+
+class RateAdapter:
+    """Streams at `source_rate` in and out of a 48 kHz batch (include/nnn_rate.h): the CLI's resampler in front of the batch, the
+    batch's ordinary call over the whole frames, and the same interpolator at the inverse ratio behind it, in one asynchronous call
+    on the GPU.  The adapter carries the partial frame and both legs' 16-sample histories from call to call: feed chunks of any size
+    (up to `max_in` samples per stream), the output does not depend on the chunking.  It borrows `batch`, which must outlive it;
+    reset, hold and resume streams on the batch as always -- a reset call also takes `reset_streams` here, a held stream sits the
+    adapter's calls out and restarts its two resampler legs from silence when it resumes."""
+
+    def __init__(self, batch, source_rate, max_in):
+        self._lib = batch._lib
+        if not hasattr(self._lib.L, "nnn_rate_create"):
+            raise RuntimeError("nnnoiseless_amd: this build of the library has no rate adapter")
+        self.batch = batch
+        self.n_streams = batch.n_streams
+        self.source_rate = float(source_rate)
+        self.max_in = int(max_in)
+        self._h = self._lib.L.nnn_rate_create(batch._h, self.source_rate, self.max_in)
+        if not self._h:
+            raise RuntimeError("nnnoiseless_amd: " + self._lib.error())
+
+    def max_output(self, n_in):
+        """Bound of the source-rate samples a call of n_in samples per stream can return."""
+        return int(self._lib.L.nnn_rate_max_output(self._h, int(n_in)))
+
+    def max_frames(self, n_in):
+        """Bound of the frames (VAD rows) such a call can complete."""
+        return int(self._lib.L.nnn_rate_max_frames(self._h, int(n_in)))
+
+    def carried(self):
+        """48 kHz samples of the partial frame now held."""
+        return int(self._lib.L.nnn_rate_carried(self._h))
+
+    def process(self, x, out=None, vad=None):
+        """x: [n_streams, n] source-rate samples, float32 (i16 range) or int16 -> (y [n_streams, n_out] of x's dtype, vad [n_frames,
+        n_streams]).  `out` ([n_streams, >= max_output(n)]) and `vad` ([>= max_frames(n), n_streams]), when handed in, are written in
+        place -- what held streams own in them stays as it was -- and views of their filled parts are returned."""
+        import ctypes as C
+        x = np.asarray(x)
+        fmt = PCM_I16 if x.dtype == np.int16 else PCM_F32
+        x = np.ascontiguousarray(x, dtype=_ffi.PCM_DTYPE[fmt])
+        if x.ndim != 2 or x.shape[0] != self.n_streams:
+            raise ValueError(f"process needs x of shape [{self.n_streams}, n], got {x.shape}")
+        n = x.shape[1]
+        out = np.zeros((self.n_streams, self.max_output(n)), x.dtype) if out is None else out
+        vad = np.zeros((self.max_frames(n), self.n_streams), np.float32) if vad is None else vad
+        if not (isinstance(out, np.ndarray) and out.ndim == 2 and out.shape[0] == self.n_streams and out.dtype == x.dtype
+                and out.flags.c_contiguous and out.flags.writeable):
+            raise ValueError("process: `out` must be a writable C-contiguous [n_streams, cap] array of x's dtype")
+        if not (isinstance(vad, np.ndarray) and vad.ndim == 2 and vad.shape[1] == self.n_streams and vad.dtype == np.float32
+                and vad.flags.c_contiguous and vad.flags.writeable):
+            raise ValueError("process: `vad` must be a writable C-contiguous float32 [cap_frames, n_streams] array")
+        n_out, n_frames = C.c_long(0), C.c_int(0)
+        self._lib.check(self._lib.L.nnn_rate_process_host(self._h, _ffi.ptr(x), n, _ffi.ptr(out), out.shape[1], C.byref(n_out), _ffi.ptr(vad),
+                                                          vad.shape[0], C.byref(n_frames), fmt))
+        self.batch.frames_done += n_frames.value
+        return out[:, :n_out.value], vad[:n_frames.value]
+
+    def process_device(self, d_in, n_in, in_stride, d_out, cap_out, out_stride, d_vad, cap_frames, fmt=PCM_F32, hip_stream=0):
+        """Raw device pointers (ints), strides in elements of `fmt`; asynchronous on hip_stream (0 = the batch's own stream).  Returns
+        (n_out, n_frames), which are host arithmetic and known at once."""
+        import ctypes as C
+        n_out, n_frames = C.c_long(0), C.c_int(0)
+        self._lib.check(self._lib.L.nnn_rate_process_device(self._h, d_in, int(n_in), int(in_stride), d_out, int(cap_out), int(out_stride),
+                                                            C.byref(n_out), d_vad, int(cap_frames), C.byref(n_frames), fmt, hip_stream))
+        self.batch.frames_done += n_frames.value
+        return n_out.value, n_frames.value
+
+    def reset(self):
+        """The adapter alone back to its fresh state (the batch has its own reset)."""
+        self._lib.check(self._lib.L.nnn_rate_reset(self._h))
+
+    def reset_streams(self, idx):
+        """The listed streams' histories and carried samples cleared from the next call on (beside batch.reset_streams(idx))."""
+        a, p = _ffi.stream_list(idx)
+        self._lib.check(self._lib.L.nnn_rate_reset_streams(self._h, p, a.size))
+
+    def tables_built(self):
+        """(up-leg, down-leg) schedule tables built so far, and the host microseconds spent on them: ((n, n), (us, us))."""
+        import ctypes as C
+        n, us = (C.c_long * 2)(), (C.c_double * 2)()
+        self._lib.check(self._lib.L.nnn_rate_debug_tables(self._h, n, us))
+        return (n[0], n[1]), (us[0], us[1])
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.L.nnn_rate_destroy(self._h)
+            self._h = None
+
+    __del__ = close
