@@ -19,6 +19,10 @@ pub struct RawNode {
 pub struct RawRate {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct RawPack {
+    _p: [u8; 0],
+}
 
 extern "C" {
     fn nnn_model_from_bytes(bytes: *const u8, len: usize) -> *mut RawModel;
@@ -161,7 +165,63 @@ extern "C" {
         n_frames: *mut c_int,
         format: c_int,
     ) -> c_int;
+    // include/nnn_pack.h
+    fn nnn_pack_create(b: *mut RawBatch, channels: c_int, step_frames: c_int) -> *mut RawPack;
+    fn nnn_pack_destroy(p: *mut RawPack);
+    fn nnn_pack_plan(
+        n_slots: c_int,
+        step_frames: c_int,
+        file_frames: *const u64,
+        n_files: c_int,
+        slot_of_file: *mut i32,
+        first_step_of_file: *mut i32,
+        summary: *mut i64,
+    ) -> c_int;
+    fn nnn_pack_run_device(
+        p: *mut RawPack,
+        d_in: *const c_void,
+        in_elems: u64,
+        in_format: c_int,
+        d_out: *mut c_void,
+        out_elems: u64,
+        out_format: c_int,
+        d_vad: *mut c_float,
+        vad_elems: u64,
+        files: *const PackFile,
+        n_files: c_int,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    fn nnn_pack_run_host(
+        p: *mut RawPack,
+        input: *const c_void,
+        in_elems: u64,
+        in_format: c_int,
+        output: *mut c_void,
+        out_elems: u64,
+        out_format: c_int,
+        vad: *mut c_float,
+        vad_elems: u64,
+        files: *const PackFile,
+        n_files: c_int,
+    ) -> c_int;
+    fn nnn_pack_last_summary(p: *const RawPack, summary: *mut i64) -> c_int;
 }
+
+/// `struct nnn_pack_file` (include/nnn_pack.h): where a file lies in the input arena, its length in sample frames (samples per channel),
+/// and where its audio and its VAD values go; offsets in elements of the respective arena's format.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct PackFile {
+    pub in_off: u64,
+    pub n_frames_samples: u64,
+    pub out_off: u64,
+    pub vad_off: u64,
+}
+
+/// The packer's input formats beside 0 (f32 in i16 range) and 1 (i16): `enum nnn_pack_format`.
+pub const PACK_I24: c_int = 16;
+pub const PACK_I32: c_int = 17;
+pub const PACK_F32_WAV: c_int = 18;
 
 /// `struct nnn_pcm_layout` (include/nnn_batch.h): the sample formats and channel interleave of the reference's callers
 /// (src/nnnoiseless.rs:147-177,301-331, src/signal.rs:95-100,123-127), converted inside the first and last kernels.
@@ -527,6 +587,101 @@ impl<'b> RateAdapter<'b> {
 impl<'b> Drop for RateAdapter<'b> {
     fn drop(&mut self) {
         unsafe { nnn_rate_destroy(self.raw) }
+    }
+}
+
+/// Files of unequal length through one batch, slots refilled (include/nnn_pack.h): every file gets, bit for bit, what the reference CLI's
+/// loop (src/nnnoiseless.rs:301-331) gives it alone -- whole frames only, the first one processed and not written -- while the batch runs
+/// full.  The packer borrows the batch for its lifetime; a run leaves it with every stream it used reset and nothing held.
+pub struct FilePacker<'b> {
+    raw: *mut RawPack,
+    batch: &'b mut BatchDenoiser,
+}
+unsafe impl<'b> Send for FilePacker<'b> {}
+
+/// steps, useful, padded, held steps, launched, held frames, files placed, the largest padding of one file (include/nnn_pack.h).
+pub type PackSummary = [i64; 8];
+
+impl<'b> FilePacker<'b> {
+    /// `None` where the backend refuses: `channels` that does not divide the batch's streams, `step_frames` above the batch's longest
+    /// group (0 = that group), a batch with more than one model.
+    pub fn new(batch: &'b mut BatchDenoiser, channels: usize, step_frames: usize) -> Option<FilePacker<'b>> {
+        let raw = unsafe { nnn_pack_create(batch.raw, channels as c_int, step_frames as c_int) };
+        if raw.is_null() {
+            None
+        } else {
+            Some(FilePacker { raw, batch })
+        }
+    }
+    pub fn batch(&mut self) -> &mut BatchDenoiser {
+        self.batch
+    }
+    /// The plan of a run over files of `frames` WHOLE frames, in slot units: `(slot_of_file, first_step_of_file, summary)`; pure host
+    /// arithmetic, the function a run itself walks.
+    pub fn plan(n_slots: usize, step_frames: usize, frames: &[u64]) -> Result<(Vec<i32>, Vec<i32>, PackSummary), ()> {
+        let (mut slot, mut first, mut s) = (vec![-1i32; frames.len()], vec![-1i32; frames.len()], [0i64; 8]);
+        let rc = unsafe {
+            nnn_pack_plan(n_slots as c_int, step_frames as c_int, frames.as_ptr(), frames.len() as c_int, slot.as_mut_ptr(), first.as_mut_ptr(), s.as_mut_ptr())
+        };
+        if rc == 0 { Ok((slot, first, s)) } else { Err(()) }
+    }
+    /// One run over host arenas of int16 samples in and out (the CLI's raw format), `vad` optional; offsets of `files` in elements.
+    /// `Err` (nothing changed) where the backend refuses the run.
+    pub fn run_i16(&mut self, input: &[i16], output: &mut [i16], vad: Option<&mut [f32]>, files: &[PackFile]) -> Result<PackSummary, ()> {
+        let (vp, vn) = match vad {
+            Some(v) => (v.as_mut_ptr(), v.len() as u64),
+            None => (std::ptr::null_mut(), 0),
+        };
+        let rc = unsafe {
+            nnn_pack_run_host(
+                self.raw,
+                input.as_ptr() as *const c_void,
+                input.len() as u64,
+                1,
+                output.as_mut_ptr() as *mut c_void,
+                output.len() as u64,
+                1,
+                vp,
+                vn,
+                files.as_ptr(),
+                files.len() as c_int,
+            )
+        };
+        if rc == 0 { Ok(self.last_summary()) } else { Err(()) }
+    }
+    /// Raw device arenas, any of the packer's formats; asynchronous on `hip_stream` (null = the batch's own stream).
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the batch's device holding the element counts given.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn run_device(
+        &mut self,
+        d_in: *const c_void,
+        in_elems: u64,
+        in_format: c_int,
+        d_out: *mut c_void,
+        out_elems: u64,
+        out_format: c_int,
+        d_vad: *mut c_float,
+        vad_elems: u64,
+        files: &[PackFile],
+        hip_stream: *mut c_void,
+    ) -> Result<PackSummary, ()> {
+        let rc = nnn_pack_run_device(
+            self.raw, d_in, in_elems, in_format, d_out, out_elems, out_format, d_vad, vad_elems, files.as_ptr(), files.len() as c_int, hip_stream,
+        );
+        if rc == 0 { Ok(self.last_summary()) } else { Err(()) }
+    }
+    /// The most recent run's summary, in stream units.
+    pub fn last_summary(&self) -> PackSummary {
+        let mut s = [0i64; 8];
+        unsafe { nnn_pack_last_summary(self.raw, s.as_mut_ptr()) };
+        s
+    }
+}
+impl<'b> Drop for FilePacker<'b> {
+    fn drop(&mut self) {
+        unsafe { nnn_pack_destroy(self.raw) }
     }
 }
 

@@ -14,6 +14,7 @@
 //
 // Everything runs in the HIP kernels behind include/nnn_batch.h; failures throw std::runtime_error.
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -26,6 +27,7 @@
 
 #include "nnn_batch.h"
 #include "nnn_node.h"
+#include "nnn_pack.h"
 #include "nnn_rate.h"
 #include "nnn_resample.h"
 #include "nnn_train.h"
@@ -391,6 +393,58 @@ class RateAdapter {
         if (rc) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
     }
     std::shared_ptr<nnn_rate> a_;
+};
+
+// Files of unequal length through one batch, slots refilled (include/nnn_pack.h): every file gets, bit for bit, what the reference CLI's loop
+// gives it alone -- whole frames only, the first one processed and not written -- while the batch runs full.  It borrows the batch, which
+// must outlive it, have one model and nothing held; a run leaves it with every stream it used reset and nothing held.
+class FilePacker {
+  public:
+    using Summary = std::array<int64_t, 8>;   // steps, useful, padded, held steps, launched, held frames, files placed, largest padding of a file
+    FilePacker(BatchDenoiser &batch, int channels = 1, int step_frames = 0) : p_(nnn_pack_create(batch.raw(), channels, step_frames), nnn_pack_destroy)
+    {
+        if (!p_) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    // the plan of a run over files of `frames` WHOLE frames, in slot units: pure host arithmetic, no batch, no device
+    static Summary plan(int n_slots, int step_frames, const std::vector<uint64_t> &frames, std::vector<int32_t> *slot_of_file = nullptr,
+                        std::vector<int32_t> *first_step_of_file = nullptr)
+    {
+        Summary s = {};
+        if (slot_of_file) slot_of_file->assign(frames.size(), -1);
+        if (first_step_of_file) first_step_of_file->assign(frames.size(), -1);
+        check(nnn_pack_plan(n_slots, step_frames, frames.data(), (int)frames.size(), slot_of_file ? slot_of_file->data() : nullptr,
+                            first_step_of_file ? first_step_of_file->data() : nullptr, s.data()));
+        return s;
+    }
+    // host arenas (synchronous); offsets of `files` in elements of the arena's format; in_format NNN_PCM_F32 / NNN_PCM_I16 / NNN_PACK_*,
+    // out_format NNN_PCM_F32 / NNN_PCM_I16; vad may be null.  Returns the run's summary in stream units.
+    Summary run(const void *in, uint64_t in_elems, int in_format, void *out, uint64_t out_elems, int out_format, float *vad, uint64_t vad_elems,
+                const std::vector<nnn_pack_file> &files)
+    {
+        check(nnn_pack_run_host(p_.get(), in, in_elems, in_format, out, out_elems, out_format, vad, vad_elems, files.data(), (int)files.size()));
+        return last_summary();
+    }
+    // device arenas; asynchronous on hip_stream (nullptr = the batch's own stream)
+    Summary run_device(const void *d_in, uint64_t in_elems, int in_format, void *d_out, uint64_t out_elems, int out_format, float *d_vad,
+                       uint64_t vad_elems, const std::vector<nnn_pack_file> &files, void *hip_stream = nullptr)
+    {
+        check(nnn_pack_run_device(p_.get(), d_in, in_elems, in_format, d_out, out_elems, out_format, d_vad, vad_elems, files.data(), (int)files.size(),
+                                  hip_stream));
+        return last_summary();
+    }
+    Summary last_summary() const
+    {
+        Summary s = {};
+        check(nnn_pack_last_summary(p_.get(), s.data()));
+        return s;
+    }
+
+  private:
+    static void check(int rc)
+    {
+        if (rc) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    std::shared_ptr<nnn_pack> p_;
 };
 
 

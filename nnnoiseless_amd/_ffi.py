@@ -40,6 +40,11 @@ RATE_SYMBOLS = [
     "nnn_rate_create", "nnn_rate_destroy", "nnn_rate_reset", "nnn_rate_reset_streams", "nnn_rate_max_output", "nnn_rate_max_frames",
     "nnn_rate_carried", "nnn_rate_process_device", "nnn_rate_process_host", "nnn_rate_debug_tables",
 ]
+# include/nnn_pack.h (the file packer; a list of its own for the same reason)
+PACK_SYMBOLS = [
+    "nnn_pack_create", "nnn_pack_destroy", "nnn_pack_plan", "nnn_pack_run_device", "nnn_pack_run_host", "nnn_pack_last_summary",
+    "nnn_pack_debug_kernels",
+]
 NODE_SYMBOLS = [
     "nnn_node_create", "nnn_node_destroy", "nnn_node_num_streams", "nnn_node_num_shards", "nnn_node_shard", "nnn_node_batch", "nnn_node_reset",
     "nnn_node_process_host", "nnn_node_process_pcm_host", "nnn_node_process_device", "nnn_node_process_device_streams", "nnn_node_synchronize",
@@ -55,6 +60,8 @@ RNNOISE_SYMBOLS = [
 
 
 PCM_F32, PCM_I16, PCM_F32_UNIT = 0, 1, 2
+PACK_I24, PACK_I32, PACK_F32_WAV = 16, 17, 18   # enum nnn_pack_format (include/nnn_pack.h): the packer's further INPUT formats
+PACK_ELEM_BYTES = {PCM_F32: 4, PCM_I16: 2, PACK_I24: 3, PACK_I32: 4, PACK_F32_WAV: 4}
 LINK_OFF, LINK_MAX, LINK_MIN = 0, 1, 2   # enum nnn_link_mode
 LINK_MODES = {"off": LINK_OFF, "max": LINK_MAX, "min": LINK_MIN}
 
@@ -84,6 +91,11 @@ class PcmLayout(C.Structure):
     """struct nnn_pcm_layout (include/nnn_batch.h)."""
     _fields_ = [("format", C.c_int), ("channels", C.c_int), ("discard_first", C.c_int), ("reserved", C.c_int),
                 ("group_stride", C.c_size_t), ("frame_stride", C.c_size_t)]
+
+
+class PackFile(C.Structure):
+    """struct nnn_pack_file (include/nnn_pack.h)."""
+    _fields_ = [("in_off", C.c_uint64), ("n_frames_samples", C.c_uint64), ("out_off", C.c_uint64), ("vad_off", C.c_uint64)]
 
 
 class BatchOpts(C.Structure):
@@ -255,6 +267,17 @@ class Library:
             L.nnn_rate_process_device.argtypes = [vp, vp, C.c_long, sz, vp, C.c_long, sz, lp, vp, i32, C.POINTER(i32), i32, vp]
             L.nnn_rate_process_host.argtypes = [vp, vp, C.c_long, vp, C.c_long, lp, vp, i32, C.POINTER(i32), i32]
             L.nnn_rate_debug_tables.argtypes = [vp, lp, C.POINTER(C.c_double)]
+        if hasattr(L, "nnn_pack_create"):
+            u64, fp_ = C.c_uint64, C.POINTER(PackFile)
+            L.nnn_pack_create.restype = vp
+            L.nnn_pack_create.argtypes = [vp, i32, i32]
+            L.nnn_pack_destroy.restype = None
+            L.nnn_pack_destroy.argtypes = [vp]
+            L.nnn_pack_plan.argtypes = [i32, i32, C.POINTER(u64), i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+            L.nnn_pack_run_device.argtypes = [vp, vp, u64, i32, vp, u64, i32, vp, u64, fp_, i32, vp]
+            L.nnn_pack_run_host.argtypes = [vp, vp, u64, i32, vp, u64, i32, vp, u64, fp_, i32]
+            L.nnn_pack_last_summary.argtypes = [vp, C.POINTER(C.c_int64)]
+            L.nnn_pack_debug_kernels.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, vp]
         L.nnn_last_error.restype = C.c_char_p
         L.rnnoise_create.restype = vp
         L.rnnoise_create.argtypes = [vp]

@@ -36,4 +36,5 @@ using namespace nnn;
 #include "nnn_batch_network.hip"
 #include "nnn_batch_debug.hip"
 #include "nnn_rate.hip"
+#include "nnn_pack.hip"
 #include "nnn_train.hip"
