@@ -20,6 +20,14 @@ pub struct RawRate {
     _p: [u8; 0],
 }
 #[repr(C)]
+pub struct RawTrain {
+    _p: [u8; 0],
+}
+#[repr(C)]
+pub struct RawSim {
+    _p: [u8; 0],
+}
+#[repr(C)]
 pub struct RawPack {
     _p: [u8; 0],
 }
@@ -205,6 +213,42 @@ extern "C" {
         n_files: c_int,
     ) -> c_int;
     fn nnn_pack_last_summary(p: *const RawPack, summary: *mut i64) -> c_int;
+    // include/nnn_train.h
+    fn nnn_train_create(n_streams: c_int, device: c_int) -> *mut RawTrain;
+    fn nnn_train_destroy(t: *mut RawTrain);
+    fn nnn_train_reset(t: *mut RawTrain) -> c_int;
+    fn nnn_train_process_host(
+        t: *mut RawTrain,
+        signal: *const c_float,
+        noise: *const c_float,
+        combined: *const c_float,
+        cutoff: *const i32,
+        vad: *const c_float,
+        rows: *mut c_float,
+        n_frames: c_int,
+    ) -> c_int;
+    // include/nnn_sim.h
+    fn nnn_sim_create(t: *mut RawTrain) -> *mut RawSim;
+    fn nnn_sim_destroy(sim: *mut RawSim);
+    fn nnn_sim_load(sim: *mut RawSim, which: c_int, pcm: *const i16, elems: u64) -> c_int;
+    fn nnn_sim_adopt_device(sim: *mut RawSim, which: c_int, d_pcm: *const i16, elems: u64) -> c_int;
+    fn nnn_sim_set_params(sim: *mut RawSim, streams: *const c_int, n: c_int, recs: *const SimParams) -> c_int;
+    fn nnn_sim_get_params(sim: *mut RawSim, streams: *const c_int, n: c_int, recs: *mut SimParams) -> c_int;
+    fn nnn_sim_reset(sim: *mut RawSim) -> c_int;
+    fn nnn_sim_process_device(sim: *mut RawSim, d_sig_off: *const u64, d_noise_off: *const u64, d_rows: *mut c_float, n_frames: c_int, hip_stream: *mut c_void) -> c_int;
+    fn nnn_sim_process_host(sim: *mut RawSim, sig_off: *const u64, noise_off: *const u64, rows: *mut c_float, n_frames: c_int) -> c_int;
+    fn nnn_sim_signals_host(
+        sim: *mut RawSim,
+        sig_off: *const u64,
+        noise_off: *const u64,
+        signal: *mut c_float,
+        noise: *mut c_float,
+        combined: *mut c_float,
+        cutoff: *mut i32,
+        vad: *mut c_float,
+        n_frames: c_int,
+    ) -> c_int;
+    fn nnn_sim_fault(sim: *mut RawSim) -> c_int;
 }
 
 /// `struct nnn_pack_file` (include/nnn_pack.h): where a file lies in the input arena, its length in sample frames (samples per channel),
@@ -682,6 +726,162 @@ impl<'b> FilePacker<'b> {
 impl<'b> Drop for FilePacker<'b> {
     fn drop(&mut self) {
         unsafe { nnn_pack_destroy(self.raw) }
+    }
+}
+
+/// The per-frame body of the reference's training-data generator (src/training.rs:113-160) for `n_streams` (clean, noise, mix)
+/// triples (include/nnn_train.h).
+pub struct TrainingFeatures {
+    raw: *mut RawTrain,
+    n_streams: usize,
+}
+unsafe impl Send for TrainingFeatures {}
+
+/// Columns of a training row: 42 features of the mix | 22 gains | 22 noise levels | vad (src/training.rs:89).
+pub const TRAIN_ROW_WIDTH: usize = 87;
+
+impl TrainingFeatures {
+    pub fn new(n_streams: usize, device: i32) -> Option<TrainingFeatures> {
+        let raw = unsafe { nnn_train_create(n_streams as c_int, device as c_int) };
+        if raw.is_null() {
+            None
+        } else {
+            Some(TrainingFeatures { raw, n_streams })
+        }
+    }
+    pub fn num_streams(&self) -> usize {
+        self.n_streams
+    }
+    /// `signal` / `noise` / `combined`: `[n_streams][n_frames][480]`; `cutoff`, `vad`: `[n_frames][n_streams]`; `rows`: `[n_frames][n_streams][87]`.
+    pub fn process(&mut self, signal: &[f32], noise: &[f32], combined: &[f32], cutoff: &[i32], vad: &[f32], rows: &mut [f32]) -> Result<(), ()> {
+        let n_frames = vad.len() / self.n_streams;
+        let (na, nl) = (self.n_streams * n_frames * 480, self.n_streams * n_frames);
+        if signal.len() != na || noise.len() != na || combined.len() != na || cutoff.len() != nl || vad.len() != nl || rows.len() != nl * TRAIN_ROW_WIDTH {
+            return Err(());
+        }
+        let rc = unsafe {
+            nnn_train_process_host(self.raw, signal.as_ptr(), noise.as_ptr(), combined.as_ptr(), cutoff.as_ptr(), vad.as_ptr(), rows.as_mut_ptr(), n_frames as c_int)
+        };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    pub fn reset(&mut self) {
+        unsafe { nnn_train_reset(self.raw) };
+    }
+}
+impl Drop for TrainingFeatures {
+    fn drop(&mut self) {
+        unsafe { nnn_train_destroy(self.raw) }
+    }
+}
+
+/// `struct nnn_sim_params` (include/nnn_sim.h): one triple's gains, its two biquads and its band cutoff.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct SimParams {
+    pub signal_gain: f32,
+    pub noise_gain: f32,
+    pub sig_a: [f32; 2],
+    pub sig_b: [f32; 2],
+    pub noise_a: [f32; 2],
+    pub noise_b: [f32; 2],
+    pub band_lp: i32,
+}
+impl Default for SimParams {
+    /// `NoiseSimulator::new` (src/training.rs:300-320): gains 1, every coefficient 0, band_lp 21.
+    fn default() -> SimParams {
+        SimParams { signal_gain: 1.0, noise_gain: 1.0, sig_a: [0.0; 2], sig_b: [0.0; 2], noise_a: [0.0; 2], noise_b: [0.0; 2], band_lp: 21 }
+    }
+}
+
+/// The generator's `NoiseSimulator` (src/training.rs:263-422) for every triple of a `TrainingFeatures`, on the device
+/// (include/nnn_sim.h): two int16 arenas of clips, per-frame offsets in, training rows (or the three signals and two labels) out.
+/// Offsets are `[n_frames][n_streams]` elements of the arenas.
+pub struct NoiseSimulator<'t> {
+    raw: *mut RawSim,
+    features: &'t mut TrainingFeatures,
+}
+unsafe impl<'t> Send for NoiseSimulator<'t> {}
+
+impl<'t> NoiseSimulator<'t> {
+    pub fn new(features: &'t mut TrainingFeatures) -> Option<NoiseSimulator<'t>> {
+        let raw = unsafe { nnn_sim_create(features.raw) };
+        if raw.is_null() {
+            None
+        } else {
+            Some(NoiseSimulator { raw, features })
+        }
+    }
+    pub fn features(&mut self) -> &mut TrainingFeatures {
+        self.features
+    }
+    pub fn load_signal(&mut self, pcm: &[i16]) -> Result<(), ()> {
+        let rc = unsafe { nnn_sim_load(self.raw, 0, pcm.as_ptr(), pcm.len() as u64) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    pub fn load_noise(&mut self, pcm: &[i16]) -> Result<(), ()> {
+        let rc = unsafe { nnn_sim_load(self.raw, 1, pcm.as_ptr(), pcm.len() as u64) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Borrows a device buffer as arena `which` (0 signal, 1 noise).
+    ///
+    /// # Safety
+    /// `d_pcm` must be device memory of the object's device holding `elems` int16 samples, valid until replaced or the simulator is dropped.
+    pub unsafe fn adopt_device(&mut self, which: i32, d_pcm: *const i16, elems: u64) -> Result<(), ()> {
+        if nnn_sim_adopt_device(self.raw, which as c_int, d_pcm, elems) == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Parameters of the listed triples, in force from the next call's first frame; `Err` (nothing changed) for a record the backend refuses.
+    pub fn set_params(&mut self, streams: &[i32], recs: &[SimParams]) -> Result<(), ()> {
+        if streams.len() != recs.len() {
+            return Err(());
+        }
+        let rc = unsafe { nnn_sim_set_params(self.raw, streams.as_ptr(), streams.len() as c_int, recs.as_ptr()) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    pub fn params(&mut self, streams: &[i32]) -> Result<Vec<SimParams>, ()> {
+        let mut recs = vec![SimParams::default(); streams.len()];
+        let rc = unsafe { nnn_sim_get_params(self.raw, streams.as_ptr(), streams.len() as c_int, recs.as_mut_ptr()) };
+        if rc == 0 { Ok(recs) } else { Err(()) }
+    }
+    /// Rows `[n_frames][n_streams][87]` for the named frames; an offset that leaves its arena refuses the call.
+    pub fn process(&mut self, sig_off: &[u64], noise_off: &[u64], rows: &mut [f32]) -> Result<(), ()> {
+        let s = self.features.n_streams;
+        if sig_off.len() != noise_off.len() || sig_off.len() % s != 0 || rows.len() != sig_off.len() * TRAIN_ROW_WIDTH {
+            return Err(());
+        }
+        let rc = unsafe { nnn_sim_process_host(self.raw, sig_off.as_ptr(), noise_off.as_ptr(), rows.as_mut_ptr(), (sig_off.len() / s) as c_int) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// The three signals `[n_streams][n_frames][480]` and the two labels `[n_frames][n_streams]` without the rows.
+    #[allow(clippy::too_many_arguments)]
+    pub fn signals(&mut self, sig_off: &[u64], noise_off: &[u64], signal: &mut [f32], noise: &mut [f32], combined: &mut [f32], cutoff: &mut [i32], vad: &mut [f32]) -> Result<(), ()> {
+        let (s, nl) = (self.features.n_streams, sig_off.len());
+        if noise_off.len() != nl || nl % s != 0 || signal.len() != nl * 480 || noise.len() != nl * 480 || combined.len() != nl * 480 || cutoff.len() != nl || vad.len() != nl {
+            return Err(());
+        }
+        let rc = unsafe {
+            nnn_sim_signals_host(self.raw, sig_off.as_ptr(), noise_off.as_ptr(), signal.as_mut_ptr(), noise.as_mut_ptr(), combined.as_mut_ptr(), cutoff.as_mut_ptr(), vad.as_mut_ptr(), (nl / s) as c_int)
+        };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Raw device pointers; asynchronous on `hip_stream` (null = the training object's own stream).
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the object's device: `n_frames x n_streams` offsets each, `n_frames x n_streams x 87` floats.
+    pub unsafe fn process_device(&mut self, d_sig_off: *const u64, d_noise_off: *const u64, d_rows: *mut c_float, n_frames: usize, hip_stream: *mut c_void) -> Result<(), ()> {
+        if nnn_sim_process_device(self.raw, d_sig_off, d_noise_off, d_rows, n_frames as c_int, hip_stream) == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Filter memories and VAD counters to zero; parameters and arenas stay.  Pair with `TrainingFeatures::reset`.
+    pub fn reset(&mut self) {
+        unsafe { nnn_sim_reset(self.raw) };
+    }
+    /// A device call met a frame outside its arena (it read as zeros).
+    pub fn fault(&mut self) -> bool {
+        unsafe { nnn_sim_fault(self.raw) > 0 }
+    }
+}
+impl<'t> Drop for NoiseSimulator<'t> {
+    fn drop(&mut self) {
+        unsafe { nnn_sim_destroy(self.raw) }
     }
 }
 

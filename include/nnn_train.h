@@ -8,8 +8,8 @@
  *     [ 42 features of the mix | 22 ideal band gains | 22 noise levels | vad ]      (src/training.rs:136-158)
  * nnn_train_process_* is that per-frame body for n_streams independent (clean, noise, mix) triples at once, on the
  * same HIP kernels as the denoiser (high-pass, pitch search, spectra, band energies, features; no RNN, no synthesis).
- * The simulator that produces the three signals, the band cutoff and the VAD label (file reading, random gains and
- * filters, src/training.rs:263-422) stays with the caller.
+ * The simulator that produces the three signals, the band cutoff and the VAD label (src/training.rs:263-422) is
+ * nnn_sim.h, an object beside this one; its file-reading and random policies are host arithmetic (offsets and parameters).
  *
  * Plain C ABI; all functions return 0 on success (nnn_last_error() of nnn_batch.h has the text); no CPU fallback.
  */

@@ -30,6 +30,7 @@
 #include "nnn_pack.h"
 #include "nnn_rate.h"
 #include "nnn_resample.h"
+#include "nnn_sim.h"
 #include "nnn_train.h"
 
 namespace nnnoiseless {
@@ -284,7 +285,7 @@ class BatchDenoiser {
 class TrainingFeatures {
   public:
     static constexpr int ROW_WIDTH = NNN_TRAIN_COLS;
-    explicit TrainingFeatures(int n_streams, int device = 0) : t_(nnn_train_create(n_streams, device), nnn_train_destroy)
+    explicit TrainingFeatures(int n_streams, int device = 0) : t_(nnn_train_create(n_streams, device), nnn_train_destroy), n_streams_(n_streams)
     {
         if (!t_) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
     }
@@ -296,9 +297,72 @@ class TrainingFeatures {
             throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
     }
     void reset() { nnn_train_reset(t_.get()); }
+    int num_streams() const { return n_streams_; }
+    nnn_train *raw() { return t_.get(); }
 
   private:
+    friend class NoiseSimulator;
     std::shared_ptr<nnn_train> t_;
+    int n_streams_ = 0;
+};
+
+// the generator's NoiseSimulator (src/training.rs:263-422) for every triple of a TrainingFeatures, on the device (nnn_sim.h): two int16
+// arenas of clips, per-frame offsets [n_frames][n_streams] in, training rows (or the three signals and the two labels) out
+class NoiseSimulator {
+  public:
+    using Params = nnn_sim_params;
+    static Params default_params() { return Params{1.0f, 1.0f, {0, 0}, {0, 0}, {0, 0}, {0, 0}, 21}; }   // NoiseSimulator::new
+    explicit NoiseSimulator(TrainingFeatures &features) : t_(features.t_), s_(nnn_sim_create(features.t_.get()), nnn_sim_destroy)
+    {
+        if (!s_) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    void load_signal(const int16_t *pcm, uint64_t elems) { check(nnn_sim_load(s_.get(), NNN_SIM_ARENA_SIGNAL, pcm, elems)); }
+    void load_noise(const int16_t *pcm, uint64_t elems) { check(nnn_sim_load(s_.get(), NNN_SIM_ARENA_NOISE, pcm, elems)); }
+    void adopt_device(int which, const int16_t *d_pcm, uint64_t elems) { check(nnn_sim_adopt_device(s_.get(), which, d_pcm, elems)); }
+    void set_params(const std::vector<int> &streams, const std::vector<Params> &recs)
+    {
+        if (streams.size() != recs.size()) throw std::invalid_argument("nnnoiseless: one record per listed stream");
+        check(nnn_sim_set_params(s_.get(), streams.data(), (int)streams.size(), recs.data()));
+    }
+    std::vector<Params> params(const std::vector<int> &streams)
+    {
+        std::vector<Params> recs(streams.size());
+        check(nnn_sim_get_params(s_.get(), streams.data(), (int)streams.size(), recs.data()));
+        return recs;
+    }
+    // host buffers: rows [n_frames][n_streams][87]; an offset that leaves its arena refuses the call
+    void process(const uint64_t *sig_off, const uint64_t *noise_off, float *rows, int n_frames)
+    {
+        check(nnn_sim_process_host(s_.get(), sig_off, noise_off, rows, n_frames));
+    }
+    // host buffers: signal / noise / combined [n_streams][n_frames][480]; cutoff, vad [n_frames][n_streams]
+    void signals(const uint64_t *sig_off, const uint64_t *noise_off, float *signal, float *noise, float *combined, int32_t *cutoff, float *vad,
+                 int n_frames)
+    {
+        check(nnn_sim_signals_host(s_.get(), sig_off, noise_off, signal, noise, combined, cutoff, vad, n_frames));
+    }
+    // raw device pointers, asynchronous on hip_stream (nullptr = the training object's own stream)
+    void process_device(const uint64_t *d_sig_off, const uint64_t *d_noise_off, float *d_rows, int n_frames, void *hip_stream = nullptr)
+    {
+        check(nnn_sim_process_device(s_.get(), d_sig_off, d_noise_off, d_rows, n_frames, hip_stream));
+    }
+    void signals_device(const uint64_t *d_sig_off, const uint64_t *d_noise_off, float *d_signal, float *d_noise, float *d_combined,
+                        int32_t *d_cutoff, float *d_vad, int n_frames, size_t stream_stride, size_t frame_stride, void *hip_stream = nullptr)
+    {
+        check(nnn_sim_signals_device(s_.get(), d_sig_off, d_noise_off, d_signal, d_noise, d_combined, d_cutoff, d_vad, n_frames, stream_stride,
+                                     frame_stride, hip_stream));
+    }
+    void reset() { check(nnn_sim_reset(s_.get())); }   // pair with TrainingFeatures::reset
+    bool fault() { return nnn_sim_fault(s_.get()) > 0; }
+    nnn_sim *raw() { return s_.get(); }
+
+  private:
+    static void check(int rc)
+    {
+        if (rc) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    std::shared_ptr<nnn_train> t_;   // (the simulator borrows the training object: kept alive here, destroyed after s_)
+    std::shared_ptr<nnn_sim> s_;
 };
 
 class DenoiseState {

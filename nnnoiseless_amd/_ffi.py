@@ -45,6 +45,11 @@ PACK_SYMBOLS = [
     "nnn_pack_create", "nnn_pack_destroy", "nnn_pack_plan", "nnn_pack_run_device", "nnn_pack_run_host", "nnn_pack_last_summary",
     "nnn_pack_debug_kernels",
 ]
+# include/nnn_sim.h (the noise simulator of the training-data generator; an object beside nnn_train)
+SIM_SYMBOLS = [
+    "nnn_sim_create", "nnn_sim_destroy", "nnn_sim_load", "nnn_sim_adopt_device", "nnn_sim_set_params", "nnn_sim_get_params", "nnn_sim_reset",
+    "nnn_sim_process_device", "nnn_sim_process_host", "nnn_sim_signals_device", "nnn_sim_signals_host", "nnn_sim_fault", "nnn_sim_debug_kernel",
+]
 NODE_SYMBOLS = [
     "nnn_node_create", "nnn_node_destroy", "nnn_node_num_streams", "nnn_node_num_shards", "nnn_node_shard", "nnn_node_batch", "nnn_node_reset",
     "nnn_node_process_host", "nnn_node_process_pcm_host", "nnn_node_process_device", "nnn_node_process_device_streams", "nnn_node_synchronize",
@@ -96,6 +101,17 @@ class PcmLayout(C.Structure):
 class PackFile(C.Structure):
     """struct nnn_pack_file (include/nnn_pack.h)."""
     _fields_ = [("in_off", C.c_uint64), ("n_frames_samples", C.c_uint64), ("out_off", C.c_uint64), ("vad_off", C.c_uint64)]
+
+
+class SimParams(C.Structure):
+    """struct nnn_sim_params (include/nnn_sim.h)."""
+    _fields_ = [("signal_gain", C.c_float), ("noise_gain", C.c_float), ("sig_a", C.c_float * 2), ("sig_b", C.c_float * 2),
+                ("noise_a", C.c_float * 2), ("noise_b", C.c_float * 2), ("band_lp", C.c_int32)]
+
+
+# the same record as a numpy dtype: what training.NoiseSimulator.params returns and set_params takes
+SIM_PARAMS_DTYPE = np.dtype([("signal_gain", "<f4"), ("noise_gain", "<f4"), ("sig_a", "<f4", 2), ("sig_b", "<f4", 2),
+                             ("noise_a", "<f4", 2), ("noise_b", "<f4", 2), ("band_lp", "<i4")])
 
 
 class BatchOpts(C.Structure):
@@ -278,6 +294,23 @@ class Library:
             L.nnn_pack_run_host.argtypes = [vp, vp, u64, i32, vp, u64, i32, vp, u64, fp_, i32]
             L.nnn_pack_last_summary.argtypes = [vp, C.POINTER(C.c_int64)]
             L.nnn_pack_debug_kernels.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, vp]
+        if hasattr(L, "nnn_sim_create"):
+            u64, ip = C.c_uint64, C.POINTER(i32)
+            L.nnn_sim_create.restype = vp
+            L.nnn_sim_create.argtypes = [vp]
+            L.nnn_sim_destroy.restype = None
+            L.nnn_sim_destroy.argtypes = [vp]
+            L.nnn_sim_load.argtypes = [vp, i32, vp, u64]
+            L.nnn_sim_adopt_device.argtypes = [vp, i32, vp, u64]
+            L.nnn_sim_set_params.argtypes = [vp, ip, i32, vp]
+            L.nnn_sim_get_params.argtypes = [vp, ip, i32, vp]
+            L.nnn_sim_reset.argtypes = [vp]
+            L.nnn_sim_process_device.argtypes = [vp, vp, vp, vp, i32, vp]
+            L.nnn_sim_process_host.argtypes = [vp, vp, vp, vp, i32]
+            L.nnn_sim_signals_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, sz, sz, vp]
+            L.nnn_sim_signals_host.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32]
+            L.nnn_sim_fault.argtypes = [vp]
+            L.nnn_sim_debug_kernel.argtypes = [vp, vp, vp, i32, i32, vp]
         L.nnn_last_error.restype = C.c_char_p
         L.rnnoise_create.restype = vp
         L.rnnoise_create.argtypes = [vp]

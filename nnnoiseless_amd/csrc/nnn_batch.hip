@@ -38,3 +38,4 @@ using namespace nnn;
 #include "nnn_rate.hip"
 #include "nnn_pack.hip"
 #include "nnn_train.hip"
+#include "nnn_sim.hip"
