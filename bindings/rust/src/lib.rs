@@ -31,6 +31,10 @@ pub struct RawSim {
 pub struct RawPack {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct RawFit {
+    _p: [u8; 0],
+}
 
 extern "C" {
     fn nnn_model_from_bytes(bytes: *const u8, len: usize) -> *mut RawModel;
@@ -249,6 +253,21 @@ extern "C" {
         n_frames: c_int,
     ) -> c_int;
     fn nnn_sim_fault(sim: *mut RawSim) -> c_int;
+    // include/nnn_fit.h
+    fn nnn_fit_create(rnn_bytes: *const u8, len: usize, max_seq: c_int, max_window: c_int, device: c_int) -> *mut RawFit;
+    fn nnn_fit_destroy(f: *mut RawFit);
+    fn nnn_fit_get(f: *mut RawFit, which: c_int, out: *mut c_float) -> c_int;
+    fn nnn_fit_set(f: *mut RawFit, which: c_int, values: *const c_float) -> c_int;
+    fn nnn_fit_get_step(f: *mut RawFit, step: *mut i64) -> c_int;
+    fn nnn_fit_set_step(f: *mut RawFit, step: i64) -> c_int;
+    fn nnn_fit_get_settings(f: *mut RawFit, s: *mut FitSettings) -> c_int;
+    fn nnn_fit_set_settings(f: *mut RawFit, s: *const FitSettings) -> c_int;
+    fn nnn_fit_export_rnn(f: *mut RawFit, out: *mut u8, cap: usize) -> c_int;
+    fn nnn_fit_forward_host(f: *mut RawFit, rows: *const c_float, n_seq: c_int, window: c_int, gains: *mut c_float, vad: *mut c_float) -> c_int;
+    fn nnn_fit_loss_host(f: *mut RawFit, rows: *const c_float, w: *const c_float, n_seq: c_int, window: c_int) -> c_int;
+    fn nnn_fit_grad_host(f: *mut RawFit, rows: *const c_float, w: *const c_float, n_seq: c_int, window: c_int) -> c_int;
+    fn nnn_fit_step(f: *mut RawFit, hip_stream: *mut c_void) -> c_int;
+    fn nnn_fit_losses(f: *mut RawFit, out: *mut c_float) -> c_int;
 }
 
 /// `struct nnn_pack_file` (include/nnn_pack.h): where a file lies in the input arena, its length in sample frames (samples per channel),
@@ -882,6 +901,109 @@ impl<'t> NoiseSimulator<'t> {
 impl<'t> Drop for NoiseSimulator<'t> {
     fn drop(&mut self) {
         unsafe { nnn_sim_destroy(self.raw) }
+    }
+}
+
+/// `struct nnn_fit_settings` (include/nnn_fit.h): Adam as Keras runs it, the L2 factor of the GRU matrices and the clip.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct FitSettings {
+    pub lr: c_float,
+    pub beta1: c_float,
+    pub beta2: c_float,
+    pub epsilon: c_float,
+    pub reg: c_float,
+    pub clip: c_float,
+}
+
+/// `{total, 10 mean(w Lg), 0.5 mean(w Lv), reg term, mean(w msse)}` of the last loss or grad call.
+pub type FitLosses = [f32; 5];
+
+/// The reference's `train/rnn_train.py` and `dump_rnn.py` on the device (include/nnn_fit.h): forward pass, loss, back-propagation
+/// through time and Adam for the 3-GRU network.  Rows are dense `[window][n_seq][87]`, weights `[window][n_seq]`.
+pub struct Trainer {
+    raw: *mut RawFit,
+}
+unsafe impl Send for Trainer {}
+
+impl Trainer {
+    pub const PARAMS: usize = 87503;
+    pub const RNN_BYTES: usize = 87521;
+    /// `template`: a `.rnn` file (its activations, its weights / 256 as the start) or `None` for the reference's training set-up
+    /// with zero parameters, to be overwritten by `set_params`.
+    pub fn new(template: Option<&[u8]>, max_seq: usize, max_window: usize, device: i32) -> Option<Trainer> {
+        let (p, n) = template.map_or((std::ptr::null(), 0), |t| (t.as_ptr(), t.len()));
+        let raw = unsafe { nnn_fit_create(p, n, max_seq as c_int, max_window as c_int, device as c_int) };
+        if raw.is_null() {
+            None
+        } else {
+            Some(Trainer { raw })
+        }
+    }
+    /// Selector 0: parameters, 1: gradient, 2 and 3: Adam's moments.
+    pub fn get(&mut self, which: i32) -> Result<Vec<f32>, ()> {
+        let mut v = vec![0.0f32; Self::PARAMS];
+        if unsafe { nnn_fit_get(self.raw, which as c_int, v.as_mut_ptr()) } == 0 { Ok(v) } else { Err(()) }
+    }
+    pub fn set(&mut self, which: i32, values: &[f32]) -> Result<(), ()> {
+        assert_eq!(values.len(), Self::PARAMS);
+        if unsafe { nnn_fit_set(self.raw, which as c_int, values.as_ptr()) } == 0 { Ok(()) } else { Err(()) }
+    }
+    pub fn params(&mut self) -> Result<Vec<f32>, ()> {
+        self.get(0)
+    }
+    pub fn set_params(&mut self, values: &[f32]) -> Result<(), ()> {
+        self.set(0, values)
+    }
+    pub fn step_count(&mut self) -> i64 {
+        let mut n = 0i64;
+        unsafe { nnn_fit_get_step(self.raw, &mut n) };
+        n
+    }
+    pub fn set_step_count(&mut self, n: i64) -> Result<(), ()> {
+        if unsafe { nnn_fit_set_step(self.raw, n) } == 0 { Ok(()) } else { Err(()) }
+    }
+    pub fn settings(&mut self) -> FitSettings {
+        let mut s = FitSettings { lr: 0.0, beta1: 0.0, beta2: 0.0, epsilon: 0.0, reg: 0.0, clip: 0.0 };
+        unsafe { nnn_fit_get_settings(self.raw, &mut s) };
+        s
+    }
+    pub fn set_settings(&mut self, s: &FitSettings) -> Result<(), ()> {
+        if unsafe { nnn_fit_set_settings(self.raw, s) } == 0 { Ok(()) } else { Err(()) }
+    }
+    /// The `.rnn` file of the current parameters (`clamp(rint(256 x), -128, 127)` behind the template's headers).
+    pub fn export_rnn(&mut self) -> Result<Vec<u8>, ()> {
+        let mut out = vec![0u8; Self::RNN_BYTES];
+        if unsafe { nnn_fit_export_rnn(self.raw, out.as_mut_ptr(), out.len()) } == 0 { Ok(out) } else { Err(()) }
+    }
+    pub fn forward(&mut self, rows: &[f32], n_seq: usize, window: usize, gains: &mut [f32], vad: &mut [f32]) -> Result<(), ()> {
+        assert!(rows.len() == n_seq * window * 87 && gains.len() == n_seq * window * 22 && vad.len() == n_seq * window);
+        let rc = unsafe { nnn_fit_forward_host(self.raw, rows.as_ptr(), n_seq as c_int, window as c_int, gains.as_mut_ptr(), vad.as_mut_ptr()) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    pub fn loss(&mut self, rows: &[f32], w: Option<&[f32]>, n_seq: usize, window: usize) -> Result<FitLosses, ()> {
+        assert!(rows.len() == n_seq * window * 87 && w.map_or(true, |w| w.len() == n_seq * window));
+        let rc = unsafe { nnn_fit_loss_host(self.raw, rows.as_ptr(), w.map_or(std::ptr::null(), |w| w.as_ptr()), n_seq as c_int, window as c_int) };
+        if rc == 0 { self.losses() } else { Err(()) }
+    }
+    /// Forward pass, loss terms and the gradient into the object.
+    pub fn grad(&mut self, rows: &[f32], w: Option<&[f32]>, n_seq: usize, window: usize) -> Result<FitLosses, ()> {
+        assert!(rows.len() == n_seq * window * 87 && w.map_or(true, |w| w.len() == n_seq * window));
+        let rc = unsafe { nnn_fit_grad_host(self.raw, rows.as_ptr(), w.map_or(std::ptr::null(), |w| w.as_ptr()), n_seq as c_int, window as c_int) };
+        if rc == 0 { self.losses() } else { Err(()) }
+    }
+    /// One Adam step from the held gradient, then the clip.
+    pub fn step(&mut self) -> Result<(), ()> {
+        if unsafe { nnn_fit_step(self.raw, std::ptr::null_mut()) } == 0 { Ok(()) } else { Err(()) }
+    }
+    pub fn losses(&mut self) -> Result<FitLosses, ()> {
+        let mut v = [0.0f32; 5];
+        if unsafe { nnn_fit_losses(self.raw, v.as_mut_ptr()) } == 0 { Ok(v) } else { Err(()) }
+    }
+}
+impl Drop for Trainer {
+    fn drop(&mut self) {
+        unsafe { nnn_fit_destroy(self.raw) }
     }
 }
 

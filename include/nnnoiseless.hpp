@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "nnn_batch.h"
+#include "nnn_fit.h"
 #include "nnn_node.h"
 #include "nnn_pack.h"
 #include "nnn_rate.h"
@@ -363,6 +364,82 @@ class NoiseSimulator {
     }
     std::shared_ptr<nnn_train> t_;   // (the simulator borrows the training object: kept alive here, destroyed after s_)
     std::shared_ptr<nnn_sim> s_;
+};
+
+// the reference's train/rnn_train.py and dump_rnn.py on the device (nnn_fit.h): forward pass, loss, BPTT and Adam for the 3-GRU network
+// over windows of consecutive training rows; host buffers are dense [window][n_seq][...]
+class Trainer {
+  public:
+    using Settings = nnn_fit_settings;
+    using Rows = nnn_fit_rows;
+    struct Losses { float total, gain, vad, reg, msse; };
+    // template_rnn empty: the reference's training set-up with zero parameters, to be overwritten by set_params
+    explicit Trainer(const std::vector<uint8_t> &template_rnn = {}, int max_seq = 32, int max_window = 2000, int device = 0)
+        : f_(nnn_fit_create(template_rnn.empty() ? nullptr : template_rnn.data(), template_rnn.size(), max_seq, max_window, device), nnn_fit_destroy)
+    {
+        if (!f_) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    std::vector<float> get(int which = NNN_FIT_SEL_PARAMS)
+    {
+        std::vector<float> v(NNN_FIT_PARAMS);
+        check(nnn_fit_get(f_.get(), which, v.data()));
+        return v;
+    }
+    void set(const std::vector<float> &v, int which = NNN_FIT_SEL_PARAMS)
+    {
+        if (v.size() != (size_t)NNN_FIT_PARAMS) throw std::invalid_argument("nnnoiseless: a parameter vector holds NNN_FIT_PARAMS values");
+        check(nnn_fit_set(f_.get(), which, v.data()));
+    }
+    int64_t step_count()
+    {
+        int64_t n = 0;
+        check(nnn_fit_get_step(f_.get(), &n));
+        return n;
+    }
+    void set_step_count(int64_t n) { check(nnn_fit_set_step(f_.get(), n)); }
+    Settings settings()
+    {
+        Settings s;
+        check(nnn_fit_get_settings(f_.get(), &s));
+        return s;
+    }
+    void set_settings(const Settings &s) { check(nnn_fit_set_settings(f_.get(), &s)); }
+    std::vector<uint8_t> export_rnn()
+    {
+        std::vector<uint8_t> out(NNN_FIT_RNN_BYTES);
+        check(nnn_fit_export_rnn(f_.get(), out.data(), out.size()));
+        return out;
+    }
+    void forward(const float *rows, int n_seq, int window, float *gains, float *vad) { check(nnn_fit_forward_host(f_.get(), rows, n_seq, window, gains, vad)); }
+    Losses loss(const float *rows, const float *w, int n_seq, int window)
+    {
+        check(nnn_fit_loss_host(f_.get(), rows, w, n_seq, window));
+        return losses();
+    }
+    Losses grad(const float *rows, const float *w, int n_seq, int window)
+    {
+        check(nnn_fit_grad_host(f_.get(), rows, w, n_seq, window));
+        return losses();
+    }
+    // raw device pointers, asynchronous on hip_stream (nullptr = the trainer's own stream)
+    void forward_device(const Rows &r, float *d_gains, float *d_vad, void *hip_stream = nullptr) { check(nnn_fit_forward_device(f_.get(), &r, d_gains, d_vad, hip_stream)); }
+    void loss_device(const Rows &r, void *hip_stream = nullptr) { check(nnn_fit_loss_device(f_.get(), &r, hip_stream)); }
+    void grad_device(const Rows &r, void *hip_stream = nullptr) { check(nnn_fit_grad_device(f_.get(), &r, hip_stream)); }
+    void step(void *hip_stream = nullptr) { check(nnn_fit_step(f_.get(), hip_stream)); }
+    Losses losses()
+    {
+        float v[5];
+        check(nnn_fit_losses(f_.get(), v));
+        return Losses{v[0], v[1], v[2], v[3], v[4]};
+    }
+    nnn_fit *raw() { return f_.get(); }
+
+  private:
+    static void check(int rc)
+    {
+        if (rc) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    std::shared_ptr<nnn_fit> f_;
 };
 
 class DenoiseState {

@@ -50,6 +50,23 @@ SIM_SYMBOLS = [
     "nnn_sim_create", "nnn_sim_destroy", "nnn_sim_load", "nnn_sim_adopt_device", "nnn_sim_set_params", "nnn_sim_get_params", "nnn_sim_reset",
     "nnn_sim_process_device", "nnn_sim_process_host", "nnn_sim_signals_device", "nnn_sim_signals_host", "nnn_sim_fault", "nnn_sim_debug_kernel",
 ]
+# include/nnn_fit.h (the network trainer: rows in, a .rnn model out)
+FIT_SYMBOLS = [
+    "nnn_fit_create", "nnn_fit_destroy", "nnn_fit_get", "nnn_fit_set", "nnn_fit_get_step", "nnn_fit_set_step", "nnn_fit_get_settings",
+    "nnn_fit_set_settings", "nnn_fit_export_rnn", "nnn_fit_forward_device", "nnn_fit_loss_device", "nnn_fit_grad_device", "nnn_fit_step",
+    "nnn_fit_losses", "nnn_fit_forward_host", "nnn_fit_loss_host", "nnn_fit_grad_host", "nnn_fit_debug_recurrence",
+]
+FIT_PARAMS, FIT_RNN_BYTES, FIT_TILE = 87503, 87521, 4
+FIT_SEL_PARAMS, FIT_SEL_GRAD, FIT_SEL_ADAM_M, FIT_SEL_ADAM_V = 0, 1, 2, 3
+# the fifteen tensors of the parameter vector (NNN_FIT_OFF_*): name -> (offset, shape)
+FIT_TENSORS = {
+    "input_dense.W": (0, (42, 24)), "input_dense.b": (1008, (24,)),
+    "vad_gru.W": (1032, (24, 72)), "vad_gru.U": (2760, (24, 72)), "vad_gru.b": (4488, (72,)),
+    "noise_gru.W": (4560, (90, 144)), "noise_gru.U": (17520, (48, 144)), "noise_gru.b": (24432, (144,)),
+    "denoise_gru.W": (24576, (114, 288)), "denoise_gru.U": (57408, (96, 288)), "denoise_gru.b": (85056, (288,)),
+    "denoise_output.W": (85344, (96, 22)), "denoise_output.b": (87456, (22,)),
+    "vad_output.W": (87478, (24, 1)), "vad_output.b": (87502, (1,)),
+}
 NODE_SYMBOLS = [
     "nnn_node_create", "nnn_node_destroy", "nnn_node_num_streams", "nnn_node_num_shards", "nnn_node_shard", "nnn_node_batch", "nnn_node_reset",
     "nnn_node_process_host", "nnn_node_process_pcm_host", "nnn_node_process_device", "nnn_node_process_device_streams", "nnn_node_synchronize",
@@ -112,6 +129,17 @@ class SimParams(C.Structure):
 # the same record as a numpy dtype: what training.NoiseSimulator.params returns and set_params takes
 SIM_PARAMS_DTYPE = np.dtype([("signal_gain", "<f4"), ("noise_gain", "<f4"), ("sig_a", "<f4", 2), ("sig_b", "<f4", 2),
                              ("noise_a", "<f4", 2), ("noise_b", "<f4", 2), ("band_lp", "<i4")])
+
+
+class FitSettings(C.Structure):
+    """struct nnn_fit_settings (include/nnn_fit.h)."""
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float), ("reg", C.c_float), ("clip", C.c_float)]
+
+
+class FitRows(C.Structure):
+    """struct nnn_fit_rows (include/nnn_fit.h)."""
+    _fields_ = [("rows", C.c_void_p), ("frame_stride", C.c_size_t), ("seq_stride", C.c_size_t), ("w", C.c_void_p),
+                ("w_frame_stride", C.c_size_t), ("w_seq_stride", C.c_size_t), ("n_seq", C.c_int), ("window", C.c_int)]
 
 
 class BatchOpts(C.Structure):
@@ -311,6 +339,28 @@ class Library:
             L.nnn_sim_signals_host.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32]
             L.nnn_sim_fault.argtypes = [vp]
             L.nnn_sim_debug_kernel.argtypes = [vp, vp, vp, i32, i32, vp]
+        if hasattr(L, "nnn_fit_create"):
+            rp, fp = C.POINTER(FitRows), C.POINTER(C.c_float)
+            L.nnn_fit_create.restype = vp
+            L.nnn_fit_create.argtypes = [C.c_char_p, sz, i32, i32, i32]
+            L.nnn_fit_destroy.restype = None
+            L.nnn_fit_destroy.argtypes = [vp]
+            L.nnn_fit_get.argtypes = [vp, i32, vp]
+            L.nnn_fit_set.argtypes = [vp, i32, vp]
+            L.nnn_fit_get_step.argtypes = [vp, C.POINTER(C.c_int64)]
+            L.nnn_fit_set_step.argtypes = [vp, C.c_int64]
+            L.nnn_fit_get_settings.argtypes = [vp, C.POINTER(FitSettings)]
+            L.nnn_fit_set_settings.argtypes = [vp, C.POINTER(FitSettings)]
+            L.nnn_fit_export_rnn.argtypes = [vp, vp, sz]
+            L.nnn_fit_forward_device.argtypes = [vp, rp, vp, vp, vp]
+            L.nnn_fit_loss_device.argtypes = [vp, rp, vp]
+            L.nnn_fit_grad_device.argtypes = [vp, rp, vp]
+            L.nnn_fit_step.argtypes = [vp, vp]
+            L.nnn_fit_losses.argtypes = [vp, fp]
+            L.nnn_fit_forward_host.argtypes = [vp, vp, i32, i32, vp, vp]
+            L.nnn_fit_loss_host.argtypes = [vp, vp, vp, i32, i32]
+            L.nnn_fit_grad_host.argtypes = [vp, vp, vp, i32, i32]
+            L.nnn_fit_debug_recurrence.argtypes = [vp, i32, i32, i32, i32, i32, vp]
         L.nnn_last_error.restype = C.c_char_p
         L.rnnoise_create.restype = vp
         L.rnnoise_create.argtypes = [vp]

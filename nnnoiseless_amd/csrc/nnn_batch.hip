@@ -39,3 +39,4 @@ using namespace nnn;
 #include "nnn_pack.hip"
 #include "nnn_train.hip"
 #include "nnn_sim.hip"
+#include "nnn_fit.hip"

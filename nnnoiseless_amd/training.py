@@ -308,7 +308,8 @@ def generate_rows(signal_clips, noise_clips, count, n_streams, seed, simulator=N
     """The generator's main loop (src/training.rs:120-161) for n_streams triples side by side: `count` rows in all, i.e.
     ceil(count / n_streams) consecutive frames per triple.  signal_clips / noise_clips: lists of int16 arrays (48 kHz mono).
     Returns rows float32 [count_per_stream, n_streams, 87].  The training script (train/rnn_train.py) windows CONSECUTIVE rows, so a
-    consumer takes them stream by stream (rows[:, s]), not frame by frame across streams.
+    consumer takes them stream by stream (rows[:, s]), not frame by frame across streams: nnnoiseless_amd.fit.windows does, and
+    nnnoiseless_amd.fit.fit trains on them.
     `simulator`: an object with load_signal / load_noise / set_params / process to use instead of a new NoiseSimulator."""
     rng = np.random.default_rng(seed)
     sig, s_starts, s_len = _arena(signal_clips)
