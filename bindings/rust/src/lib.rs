@@ -35,6 +35,10 @@ pub struct RawPack {
 pub struct RawFit {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct RawScore {
+    _p: [u8; 0],
+}
 
 extern "C" {
     fn nnn_model_from_bytes(bytes: *const u8, len: usize) -> *mut RawModel;
@@ -268,6 +272,26 @@ extern "C" {
     fn nnn_fit_grad_host(f: *mut RawFit, rows: *const c_float, w: *const c_float, n_seq: c_int, window: c_int) -> c_int;
     fn nnn_fit_step(f: *mut RawFit, hip_stream: *mut c_void) -> c_int;
     fn nnn_fit_losses(f: *mut RawFit, out: *mut c_float) -> c_int;
+    // include/nnn_score.h
+    fn nnn_score_create(n_streams: c_int, max_delay: c_int, device: c_int) -> *mut RawScore;
+    fn nnn_score_destroy(h: *mut RawScore);
+    fn nnn_score_set_delay(h: *mut RawScore, idx: *const c_int, n: c_int, delays: *const i32) -> c_int;
+    fn nnn_score_get_delay(h: *mut RawScore, idx: *const c_int, n: c_int, delays: *mut i32) -> c_int;
+    fn nnn_score_reset(h: *mut RawScore, idx: *const c_int, n: c_int) -> c_int;
+    fn nnn_score_accumulate_device(
+        h: *mut RawScore,
+        d_ref: *const c_float,
+        d_test: *const c_float,
+        d_valid: *const u8,
+        d_frame_sums: *mut f64,
+        n_frames: c_int,
+        stream_stride: usize,
+        frame_stride: usize,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    fn nnn_score_accumulate_host(h: *mut RawScore, reference: *const c_float, test: *const c_float, valid: *const u8, frame_sums: *mut f64, n_frames: c_int) -> c_int;
+    fn nnn_score_totals(h: *mut RawScore, out: *mut f64, counts: *mut u64) -> c_int;
+    fn nnn_score_totals_device(h: *mut RawScore, d_out: *mut f64, d_counts: *mut u64, hip_stream: *mut c_void) -> c_int;
 }
 
 /// `struct nnn_pack_file` (include/nnn_pack.h): where a file lies in the input arena, its length in sample frames (samples per channel),
@@ -1004,6 +1028,105 @@ impl Trainer {
 impl Drop for Trainer {
     fn drop(&mut self) {
         unsafe { nnn_fit_destroy(self.raw) }
+    }
+}
+
+/// Per-stream sums between a reference and a test signal, carried across calls on the device (include/nnn_score.h): per stream
+/// `[A, B, C, E] = [sum r^2, sum y^2, sum r y, sum (r - y)^2]` in f64 in one fixed order, the reference delayed by the stream's delay.
+/// Host buffers are dense `[n_streams][n_frames][480]`, the mask `[n_frames][n_streams]`, frame sums `[n_frames][n_streams][4]`.
+pub struct Scorer {
+    raw: *mut RawScore,
+    n_streams: usize,
+}
+unsafe impl Send for Scorer {}
+
+impl Scorer {
+    pub const MAX_DELAY: usize = 960;
+    pub fn new(n_streams: usize, max_delay: usize, device: i32) -> Option<Scorer> {
+        let raw = unsafe { nnn_score_create(n_streams as c_int, max_delay as c_int, device as c_int) };
+        if raw.is_null() {
+            None
+        } else {
+            Some(Scorer { raw, n_streams })
+        }
+    }
+    pub fn num_streams(&self) -> usize {
+        self.n_streams
+    }
+    /// Delays of the listed streams (`None`: one per stream); also zeroes their history, totals and count.
+    pub fn set_delay(&mut self, idx: Option<&[i32]>, delays: &[i32]) -> Result<(), ()> {
+        assert_eq!(delays.len(), idx.map_or(self.n_streams, |i| i.len()));
+        let rc = unsafe { nnn_score_set_delay(self.raw, idx.map_or(std::ptr::null(), |i| i.as_ptr()), delays.len() as c_int, delays.as_ptr()) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    pub fn delay(&mut self) -> Vec<i32> {
+        let mut d = vec![0i32; self.n_streams];
+        unsafe { nnn_score_get_delay(self.raw, std::ptr::null(), self.n_streams as c_int, d.as_mut_ptr()) };
+        d
+    }
+    /// History, totals and count of the listed streams (`None`: all) to zero; the delays stay.
+    pub fn reset(&mut self, idx: Option<&[i32]>) -> Result<(), ()> {
+        let rc = unsafe { nnn_score_reset(self.raw, idx.map_or(std::ptr::null(), |i| i.as_ptr()), idx.map_or(0, |i| i.len()) as c_int) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    pub fn accumulate(&mut self, reference: &[f32], test: &[f32], n_frames: usize, valid: Option<&[u8]>, frame_sums: Option<&mut [f64]>) -> Result<(), ()> {
+        let rows = self.n_streams * n_frames;
+        assert!(reference.len() == rows * 480 && test.len() == rows * 480 && valid.map_or(true, |v| v.len() == rows));
+        assert!(frame_sums.as_ref().map_or(true, |f| f.len() == rows * 4));
+        let rc = unsafe {
+            nnn_score_accumulate_host(
+                self.raw,
+                reference.as_ptr(),
+                test.as_ptr(),
+                valid.map_or(std::ptr::null(), |v| v.as_ptr()),
+                frame_sums.map_or(std::ptr::null_mut(), |f| f.as_mut_ptr()),
+                n_frames as c_int,
+            )
+        };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Raw device pointers, asynchronous on `hip_stream` (null: the scorer's own stream); strides in floats.
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the sizes include/nnn_score.h states, valid until the call has run.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn accumulate_device(
+        &mut self,
+        d_ref: *const f32,
+        d_test: *const f32,
+        d_valid: *const u8,
+        d_frame_sums: *mut f64,
+        n_frames: usize,
+        stream_stride: usize,
+        frame_stride: usize,
+        hip_stream: *mut c_void,
+    ) -> Result<(), ()> {
+        let rc = nnn_score_accumulate_device(self.raw, d_ref, d_test, d_valid, d_frame_sums, n_frames as c_int, stream_stride, frame_stride, hip_stream);
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// `([n_streams][4] sums, [n_streams] frames counted)`; waits for the calls made so far.
+    pub fn totals(&mut self) -> Result<(Vec<[f64; 4]>, Vec<u64>), ()> {
+        let mut t = vec![[0.0f64; 4]; self.n_streams];
+        let mut c = vec![0u64; self.n_streams];
+        if unsafe { nnn_score_totals(self.raw, t.as_mut_ptr() as *mut f64, c.as_mut_ptr()) } == 0 { Ok((t, c)) } else { Err(()) }
+    }
+    /// # Safety
+    /// Device memory for `[n_streams][4]` doubles and `[n_streams]` counts (either may be null).
+    pub unsafe fn totals_device(&mut self, d_out: *mut f64, d_counts: *mut u64, hip_stream: *mut c_void) -> Result<(), ()> {
+        if nnn_score_totals_device(self.raw, d_out, d_counts, hip_stream) == 0 { Ok(()) } else { Err(()) }
+    }
+    /// `10 log10(A / E)`; inf or nan for zero denominators, as IEEE division and the logarithm give.
+    pub fn snr_db(a: f64, e: f64) -> f64 {
+        10.0 * (a / e).log10()
+    }
+    /// `10 log10(C^2 / (A B - C^2))`.
+    pub fn si_sdr_db(a: f64, b: f64, c: f64) -> f64 {
+        10.0 * (c * c / (a * b - c * c)).log10()
+    }
+}
+impl Drop for Scorer {
+    fn drop(&mut self) {
+        unsafe { nnn_score_destroy(self.raw) }
     }
 }
 

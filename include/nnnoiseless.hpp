@@ -31,6 +31,7 @@
 #include "nnn_pack.h"
 #include "nnn_rate.h"
 #include "nnn_resample.h"
+#include "nnn_score.h"
 #include "nnn_sim.h"
 #include "nnn_train.h"
 
@@ -440,6 +441,66 @@ class Trainer {
         if (rc) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
     }
     std::shared_ptr<nnn_fit> f_;
+};
+
+// per-stream sums between a reference and a test signal, carried across calls on the device (nnn_score.h): A = sum r^2, B = sum y^2,
+// C = sum r y, E = sum (r - y)^2 in f64, in one fixed order; SNR and SI-SDR are host arithmetic on them
+class Scorer {
+  public:
+    struct Totals {
+        std::vector<double> sums;        // [n_streams][4]: A, B, C, E
+        std::vector<uint64_t> frames;    // [n_streams]
+    };
+    explicit Scorer(int n_streams, int max_delay = NNN_SCORE_MAX_DELAY, int device = 0)
+        : n_(n_streams), h_(nnn_score_create(n_streams, max_delay, device), nnn_score_destroy)
+    {
+        if (!h_) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    int num_streams() const { return n_; }
+    // delays of the listed streams (idx empty: one per stream); also zeroes their history, totals and count
+    void set_delay(const std::vector<int> &idx, const std::vector<int32_t> &delays)
+    {
+        if (delays.size() != (idx.empty() ? (size_t)n_ : idx.size())) throw std::invalid_argument("nnnoiseless: one delay per listed stream");
+        check(nnn_score_set_delay(h_.get(), idx.empty() ? nullptr : idx.data(), (int)delays.size(), delays.data()));
+    }
+    std::vector<int32_t> delay()
+    {
+        std::vector<int32_t> d((size_t)n_);
+        check(nnn_score_get_delay(h_.get(), nullptr, n_, d.data()));
+        return d;
+    }
+    // idx empty: every stream
+    void reset(const std::vector<int> &idx = {}) { check(nnn_score_reset(h_.get(), idx.empty() ? nullptr : idx.data(), (int)idx.size())); }
+    // host memory, dense [n_streams][n_frames][480]; valid nullptr or [n_frames][n_streams]; frame_sums nullptr or [n_frames][n_streams][4]
+    void accumulate(const float *ref, const float *test, int n_frames, const uint8_t *valid = nullptr, double *frame_sums = nullptr)
+    {
+        check(nnn_score_accumulate_host(h_.get(), ref, test, valid, frame_sums, n_frames));
+    }
+    // raw device pointers, asynchronous on hip_stream (nullptr = the scorer's own stream); strides in floats
+    void accumulate_device(const float *d_ref, const float *d_test, int n_frames, size_t stream_stride, size_t frame_stride,
+                           const uint8_t *d_valid = nullptr, double *d_frame_sums = nullptr, void *hip_stream = nullptr)
+    {
+        check(nnn_score_accumulate_device(h_.get(), d_ref, d_test, d_valid, d_frame_sums, n_frames, stream_stride, frame_stride, hip_stream));
+    }
+    Totals totals()
+    {
+        Totals t{std::vector<double>((size_t)n_ * NNN_SCORE_SUMS), std::vector<uint64_t>((size_t)n_)};
+        check(nnn_score_totals(h_.get(), t.sums.data(), t.frames.data()));
+        return t;
+    }
+    void totals_device(double *d_out, uint64_t *d_counts, void *hip_stream = nullptr) { check(nnn_score_totals_device(h_.get(), d_out, d_counts, hip_stream)); }
+    // the figures, as nnnoiseless_amd/score.py has them: inf or nan for zero denominators, as IEEE division and log10 give
+    static double snr_db(double A, double E) { return 10.0 * std::log10(A / E); }
+    static double si_sdr_db(double A, double B, double C) { return 10.0 * std::log10(C * C / (A * B - C * C)); }
+    nnn_score *raw() { return h_.get(); }
+
+  private:
+    static void check(int rc)
+    {
+        if (rc) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    int n_;
+    std::shared_ptr<nnn_score> h_;
 };
 
 class DenoiseState {

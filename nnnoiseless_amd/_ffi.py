@@ -56,6 +56,12 @@ FIT_SYMBOLS = [
     "nnn_fit_set_settings", "nnn_fit_export_rnn", "nnn_fit_forward_device", "nnn_fit_loss_device", "nnn_fit_grad_device", "nnn_fit_step",
     "nnn_fit_losses", "nnn_fit_forward_host", "nnn_fit_loss_host", "nnn_fit_grad_host", "nnn_fit_debug_recurrence",
 ]
+# include/nnn_score.h (the scorer: sums between a reference and a test signal; an object beside the simulator and the trainer)
+SCORE_SYMBOLS = [
+    "nnn_score_create", "nnn_score_destroy", "nnn_score_set_delay", "nnn_score_get_delay", "nnn_score_reset", "nnn_score_accumulate_device",
+    "nnn_score_accumulate_host", "nnn_score_totals", "nnn_score_totals_device",
+]
+SCORE_MAX_DELAY, SCORE_SUMS = 960, 4
 FIT_PARAMS, FIT_RNN_BYTES, FIT_TILE = 87503, 87521, 4
 FIT_SEL_PARAMS, FIT_SEL_GRAD, FIT_SEL_ADAM_M, FIT_SEL_ADAM_V = 0, 1, 2, 3
 # the fifteen tensors of the parameter vector (NNN_FIT_OFF_*): name -> (offset, shape)
@@ -361,6 +367,19 @@ class Library:
             L.nnn_fit_loss_host.argtypes = [vp, vp, vp, i32, i32]
             L.nnn_fit_grad_host.argtypes = [vp, vp, vp, i32, i32]
             L.nnn_fit_debug_recurrence.argtypes = [vp, i32, i32, i32, i32, i32, vp]
+        if hasattr(L, "nnn_score_create"):
+            ip = C.POINTER(i32)
+            L.nnn_score_create.restype = vp
+            L.nnn_score_create.argtypes = [i32, i32, i32]
+            L.nnn_score_destroy.restype = None
+            L.nnn_score_destroy.argtypes = [vp]
+            L.nnn_score_set_delay.argtypes = [vp, ip, i32, vp]
+            L.nnn_score_get_delay.argtypes = [vp, ip, i32, vp]
+            L.nnn_score_reset.argtypes = [vp, ip, i32]
+            L.nnn_score_accumulate_device.argtypes = [vp, vp, vp, vp, vp, i32, sz, sz, vp]
+            L.nnn_score_accumulate_host.argtypes = [vp, vp, vp, vp, vp, i32]
+            L.nnn_score_totals.argtypes = [vp, vp, vp]
+            L.nnn_score_totals_device.argtypes = [vp, vp, vp, vp]
         L.nnn_last_error.restype = C.c_char_p
         L.rnnoise_create.restype = vp
         L.rnnoise_create.argtypes = [vp]

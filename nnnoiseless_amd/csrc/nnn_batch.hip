@@ -40,3 +40,4 @@ using namespace nnn;
 #include "nnn_train.hip"
 #include "nnn_sim.hip"
 #include "nnn_fit.hip"
+#include "nnn_score.hip"
