@@ -39,6 +39,10 @@ pub struct RawFit {
 pub struct RawScore {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct RawGate {
+    _p: [u8; 0],
+}
 
 extern "C" {
     fn nnn_model_from_bytes(bytes: *const u8, len: usize) -> *mut RawModel;
@@ -292,6 +296,50 @@ extern "C" {
     fn nnn_score_accumulate_host(h: *mut RawScore, reference: *const c_float, test: *const c_float, valid: *const u8, frame_sums: *mut f64, n_frames: c_int) -> c_int;
     fn nnn_score_totals(h: *mut RawScore, out: *mut f64, counts: *mut u64) -> c_int;
     fn nnn_score_totals_device(h: *mut RawScore, d_out: *mut f64, d_counts: *mut u64, hip_stream: *mut c_void) -> c_int;
+    // include/nnn_gate.h
+    fn nnn_gate_create(n_streams: c_int, max_lookback: c_int, device: c_int) -> *mut RawGate;
+    fn nnn_gate_destroy(g: *mut RawGate);
+    fn nnn_gate_set_params(g: *mut RawGate, idx: *const c_int, n: c_int, params: *const GateParams) -> c_int;
+    fn nnn_gate_get_params(g: *mut RawGate, idx: *const c_int, n: c_int, params: *mut GateParams) -> c_int;
+    fn nnn_gate_reset(g: *mut RawGate, idx: *const c_int, n: c_int) -> c_int;
+    fn nnn_gate_apply_device(
+        g: *mut RawGate,
+        d_in: *const c_float,
+        d_out: *mut c_float,
+        d_vad: *const c_float,
+        d_live: *const u8,
+        d_open: *mut u8,
+        n_frames: c_int,
+        stream_stride: usize,
+        frame_stride: usize,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    fn nnn_gate_apply_pcm_device(
+        g: *mut RawGate,
+        d_in: *const c_void,
+        d_out: *mut c_void,
+        d_vad: *const c_float,
+        d_live: *const u8,
+        d_open: *mut u8,
+        n_frames: c_int,
+        layout: *const PcmLayout,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    fn nnn_gate_apply_host(g: *mut RawGate, input: *const c_float, out: *mut c_float, vad: *const c_float, live: *const u8, open: *mut u8, n_frames: c_int) -> c_int;
+    fn nnn_gate_state_bytes(g: *const RawGate) -> usize;
+    fn nnn_gate_export_streams(g: *mut RawGate, idx: *const c_int, n: c_int, records: *mut c_void, bytes: usize) -> c_int;
+    fn nnn_gate_import_streams(g: *mut RawGate, idx: *const c_int, n: c_int, records: *const c_void, bytes: usize) -> c_int;
+}
+
+/// `struct nnn_gate_params` (include/nnn_gate.h): a stream's gate.  `threshold` and `level` in [0, 1], `grace` 0 ..= 6000 frames,
+/// `lookback` 0 ..= the object's `max_lookback` frames.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct GateParams {
+    pub threshold: f32,
+    pub grace: i32,
+    pub lookback: i32,
+    pub level: f32,
 }
 
 /// `struct nnn_pack_file` (include/nnn_pack.h): where a file lies in the input arena, its length in sample frames (samples per channel),
@@ -1127,6 +1175,123 @@ impl Scorer {
 impl Drop for Scorer {
     fn drop(&mut self) {
         unsafe { nnn_score_destroy(self.raw) }
+    }
+}
+
+/// The VAD gate behind the denoiser (include/nnn_gate.h): per stream a threshold on the speech probability, a grace period, a look-back
+/// that delays the audio a few frames so the onset is not cut, and a gain for the closed gate (0 = mute).  Host buffers are dense
+/// `[n_streams][n_frames][480]`, VAD and open flags `[n_frames][n_streams]`, the live mask `[n_streams]`.
+pub struct VadGate {
+    raw: *mut RawGate,
+    n_streams: usize,
+}
+unsafe impl Send for VadGate {}
+
+impl VadGate {
+    pub const MAX_LOOKBACK: usize = 8;
+    pub const MAX_GRACE: usize = 6000;
+    pub fn new(n_streams: usize, max_lookback: usize, device: i32) -> Option<VadGate> {
+        let raw = unsafe { nnn_gate_create(n_streams as c_int, max_lookback as c_int, device as c_int) };
+        if raw.is_null() {
+            None
+        } else {
+            Some(VadGate { raw, n_streams })
+        }
+    }
+    pub fn num_streams(&self) -> usize {
+        self.n_streams
+    }
+    /// Bytes of one exported record.
+    pub fn state_bytes(&self) -> usize {
+        unsafe { nnn_gate_state_bytes(self.raw) }
+    }
+    /// Parameters of the listed streams (`None`: one per stream); also resets those streams.
+    pub fn set_params(&mut self, idx: Option<&[i32]>, params: &[GateParams]) -> Result<(), ()> {
+        assert_eq!(params.len(), idx.map_or(self.n_streams, |i| i.len()));
+        let rc = unsafe { nnn_gate_set_params(self.raw, idx.map_or(std::ptr::null(), |i| i.as_ptr()), params.len() as c_int, params.as_ptr()) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    pub fn params(&mut self) -> Vec<GateParams> {
+        let mut p = vec![GateParams::default(); self.n_streams];
+        unsafe { nnn_gate_get_params(self.raw, std::ptr::null(), self.n_streams as c_int, p.as_mut_ptr()) };
+        p
+    }
+    /// The listed streams (`None`: all) back to "never voiced, closed, no history"; the parameters stay.
+    pub fn reset(&mut self, idx: Option<&[i32]>) -> Result<(), ()> {
+        let rc = unsafe { nnn_gate_reset(self.raw, idx.map_or(std::ptr::null(), |i| i.as_ptr()), idx.map_or(0, |i| i.len()) as c_int) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// In place on host memory; what a stream marked 0 in `live` owns is left as it was.
+    pub fn apply(&mut self, audio: &mut [f32], vad: &[f32], n_frames: usize, live: Option<&[u8]>, open: Option<&mut [u8]>) -> Result<(), ()> {
+        let rows = self.n_streams * n_frames;
+        assert!(audio.len() == rows * 480 && vad.len() == rows && live.map_or(true, |l| l.len() == self.n_streams));
+        assert!(open.as_ref().map_or(true, |o| o.len() == rows));
+        let rc = unsafe {
+            nnn_gate_apply_host(
+                self.raw,
+                audio.as_ptr(),
+                audio.as_mut_ptr(),
+                vad.as_ptr(),
+                live.map_or(std::ptr::null(), |l| l.as_ptr()),
+                open.map_or(std::ptr::null_mut(), |o| o.as_mut_ptr()),
+                n_frames as c_int,
+            )
+        };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Raw device pointers, asynchronous on `hip_stream` (null: the gate's own stream); strides in floats; `d_out == d_in` is in place.
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the sizes include/nnn_gate.h states, valid until the call has run.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn apply_device(
+        &mut self,
+        d_in: *const f32,
+        d_out: *mut f32,
+        d_vad: *const f32,
+        d_live: *const u8,
+        d_open: *mut u8,
+        n_frames: usize,
+        stream_stride: usize,
+        frame_stride: usize,
+        hip_stream: *mut c_void,
+    ) -> Result<(), ()> {
+        let rc = nnn_gate_apply_device(self.raw, d_in, d_out, d_vad, d_live, d_open, n_frames as c_int, stream_stride, frame_stride, hip_stream);
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// The packed boundary of `BatchDenoiser::process_pcm_device`.
+    ///
+    /// # Safety
+    /// As `apply_device`, in elements of the layout's format.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn apply_pcm_device(
+        &mut self,
+        d_in: *const c_void,
+        d_out: *mut c_void,
+        d_vad: *const f32,
+        d_live: *const u8,
+        d_open: *mut u8,
+        n_frames: usize,
+        layout: &PcmLayout,
+        hip_stream: *mut c_void,
+    ) -> Result<(), ()> {
+        let rc = nnn_gate_apply_pcm_device(self.raw, d_in, d_out, d_vad, d_live, d_open, n_frames as c_int, layout, hip_stream);
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Records of `state_bytes()` bytes each: a stream moved to another gate continues bit for bit.
+    pub fn export_streams(&mut self, idx: &[i32]) -> Result<Vec<u8>, ()> {
+        let mut rec = vec![0u8; idx.len() * self.state_bytes()];
+        let rc = unsafe { nnn_gate_export_streams(self.raw, idx.as_ptr(), idx.len() as c_int, rec.as_mut_ptr() as *mut c_void, rec.len()) };
+        if rc == 0 { Ok(rec) } else { Err(()) }
+    }
+    pub fn import_streams(&mut self, idx: &[i32], records: &[u8]) -> Result<(), ()> {
+        let rc = unsafe { nnn_gate_import_streams(self.raw, idx.as_ptr(), idx.len() as c_int, records.as_ptr() as *const c_void, records.len()) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+}
+impl Drop for VadGate {
+    fn drop(&mut self) {
+        unsafe { nnn_gate_destroy(self.raw) }
     }
 }
 

@@ -27,6 +27,7 @@
 
 #include "nnn_batch.h"
 #include "nnn_fit.h"
+#include "nnn_gate.h"
 #include "nnn_node.h"
 #include "nnn_pack.h"
 #include "nnn_rate.h"
@@ -501,6 +502,75 @@ class Scorer {
     }
     int n_;
     std::shared_ptr<nnn_score> h_;
+};
+
+// the VAD gate behind the denoiser (nnn_gate.h): per stream a threshold on the speech probability, a grace period, a look-back that delays
+// the audio a few frames so the onset is not cut, and a gain for the closed gate (0 = mute); the rule is exact and stated in the header
+class VadGate {
+  public:
+    explicit VadGate(int n_streams, int max_lookback = 0, int device = 0)
+        : n_(n_streams), h_(nnn_gate_create(n_streams, max_lookback, device), nnn_gate_destroy)
+    {
+        if (!h_) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    int num_streams() const { return n_; }
+    // parameters of the listed streams (idx empty: one per stream); also resets those streams
+    void set_params(const std::vector<nnn_gate_params> &params, const std::vector<int> &idx = {})
+    {
+        if (params.size() != (idx.empty() ? (size_t)n_ : idx.size())) throw std::invalid_argument("nnnoiseless: one parameter record per listed stream");
+        check(nnn_gate_set_params(h_.get(), idx.empty() ? nullptr : idx.data(), (int)params.size(), params.data()));
+    }
+    // the same parameters for every stream
+    void set_params(float threshold, int grace, int lookback, float level)
+    {
+        set_params(std::vector<nnn_gate_params>((size_t)n_, nnn_gate_params{threshold, grace, lookback, level}));
+    }
+    std::vector<nnn_gate_params> params()
+    {
+        std::vector<nnn_gate_params> p((size_t)n_);
+        check(nnn_gate_get_params(h_.get(), nullptr, n_, p.data()));
+        return p;
+    }
+    // idx empty: every stream
+    void reset(const std::vector<int> &idx = {}) { check(nnn_gate_reset(h_.get(), idx.empty() ? nullptr : idx.data(), (int)idx.size())); }
+    // host memory, dense [n_streams][n_frames][480] (out may be in); vad [n_frames][n_streams]; live nullptr or [n_streams]; open nullptr or
+    // [n_frames][n_streams]
+    void apply(const float *in, float *out, const float *vad, int n_frames, const uint8_t *live = nullptr, uint8_t *open = nullptr)
+    {
+        check(nnn_gate_apply_host(h_.get(), in, out, vad, live, open, n_frames));
+    }
+    // raw device pointers, asynchronous on hip_stream (nullptr = the gate's own stream); strides in floats; d_out == d_in is in place
+    void apply_device(const float *d_in, float *d_out, const float *d_vad, int n_frames, size_t stream_stride, size_t frame_stride,
+                      const uint8_t *d_live = nullptr, uint8_t *d_open = nullptr, void *hip_stream = nullptr)
+    {
+        check(nnn_gate_apply_device(h_.get(), d_in, d_out, d_vad, d_live, d_open, n_frames, stream_stride, frame_stride, hip_stream));
+    }
+    // the packed boundary of BatchDenoiser::process_pcm_device
+    void apply_pcm_device(const void *d_in, void *d_out, const float *d_vad, int n_frames, const nnn_pcm_layout &layout, const uint8_t *d_live = nullptr,
+                          uint8_t *d_open = nullptr, void *hip_stream = nullptr)
+    {
+        check(nnn_gate_apply_pcm_device(h_.get(), d_in, d_out, d_vad, d_live, d_open, n_frames, &layout, hip_stream));
+    }
+    // records of NNN_GATE_STATE_BYTES bytes each: a stream moved to another gate continues bit for bit
+    std::vector<uint8_t> export_streams(const std::vector<int> &idx)
+    {
+        std::vector<uint8_t> rec(idx.size() * (size_t)NNN_GATE_STATE_BYTES);
+        check(nnn_gate_export_streams(h_.get(), idx.data(), (int)idx.size(), rec.data(), rec.size()));
+        return rec;
+    }
+    void import_streams(const std::vector<int> &idx, const std::vector<uint8_t> &records)
+    {
+        check(nnn_gate_import_streams(h_.get(), idx.data(), (int)idx.size(), records.data(), records.size()));
+    }
+    nnn_gate *raw() { return h_.get(); }
+
+  private:
+    static void check(int rc)
+    {
+        if (rc) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    int n_;
+    std::shared_ptr<nnn_gate> h_;
 };
 
 class DenoiseState {

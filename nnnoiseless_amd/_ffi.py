@@ -62,6 +62,18 @@ SCORE_SYMBOLS = [
     "nnn_score_accumulate_host", "nnn_score_totals", "nnn_score_totals_device",
 ]
 SCORE_MAX_DELAY, SCORE_SUMS = 960, 4
+# include/nnn_gate.h (the VAD gate: threshold, grace and look-back per stream behind the denoiser; an object beside the batch)
+GATE_SYMBOLS = [
+    "nnn_gate_create", "nnn_gate_destroy", "nnn_gate_set_params", "nnn_gate_get_params", "nnn_gate_reset", "nnn_gate_apply_device",
+    "nnn_gate_apply_pcm_device", "nnn_gate_apply_host", "nnn_gate_state_bytes", "nnn_gate_export_streams", "nnn_gate_import_streams",
+]
+GATE_MAX_LOOKBACK, GATE_MAX_GRACE, GATE_NEVER = 8, 6000, 0x7fffffff
+GATE_STATE_BYTES, GATE_STATE_VERSION, GATE_STATE_MAGIC = 48 + 8 * 480 * 4, 1, 0x3147564E
+# struct nnn_gate_params as a numpy dtype: what VadGate.params returns
+GATE_PARAMS_DTYPE = np.dtype([("threshold", "<f4"), ("grace", "<i4"), ("lookback", "<i4"), ("level", "<f4")])
+# a stream's record (NNN_GATE_STATE_BYTES): the header's fields and the history rows
+GATE_STATE_DTYPE = np.dtype([("magic", "<u4"), ("version", "<u4"), ("size", "<u4"), ("threshold", "<f4"), ("grace", "<i4"), ("lookback", "<i4"),
+                             ("level", "<f4"), ("since", "<i4"), ("was_open", "<u4"), ("zero", "<u4", 3), ("history", "<f4", (8, 480))])
 FIT_PARAMS, FIT_RNN_BYTES, FIT_TILE = 87503, 87521, 4
 FIT_SEL_PARAMS, FIT_SEL_GRAD, FIT_SEL_ADAM_M, FIT_SEL_ADAM_V = 0, 1, 2, 3
 # the fifteen tensors of the parameter vector (NNN_FIT_OFF_*): name -> (offset, shape)
@@ -380,6 +392,22 @@ class Library:
             L.nnn_score_accumulate_host.argtypes = [vp, vp, vp, vp, vp, i32]
             L.nnn_score_totals.argtypes = [vp, vp, vp]
             L.nnn_score_totals_device.argtypes = [vp, vp, vp, vp]
+        if hasattr(L, "nnn_gate_create"):
+            ip = C.POINTER(i32)
+            L.nnn_gate_create.restype = vp
+            L.nnn_gate_create.argtypes = [i32, i32, i32]
+            L.nnn_gate_destroy.restype = None
+            L.nnn_gate_destroy.argtypes = [vp]
+            L.nnn_gate_set_params.argtypes = [vp, ip, i32, vp]
+            L.nnn_gate_get_params.argtypes = [vp, ip, i32, vp]
+            L.nnn_gate_reset.argtypes = [vp, ip, i32]
+            L.nnn_gate_apply_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, sz, sz, vp]
+            L.nnn_gate_apply_pcm_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, C.POINTER(PcmLayout), vp]
+            L.nnn_gate_apply_host.argtypes = [vp, vp, vp, vp, vp, vp, i32]
+            L.nnn_gate_state_bytes.restype = sz
+            L.nnn_gate_state_bytes.argtypes = [vp]
+            L.nnn_gate_export_streams.argtypes = [vp, ip, i32, vp, sz]
+            L.nnn_gate_import_streams.argtypes = [vp, ip, i32, vp, sz]
         L.nnn_last_error.restype = C.c_char_p
         L.rnnoise_create.restype = vp
         L.rnnoise_create.argtypes = [vp]

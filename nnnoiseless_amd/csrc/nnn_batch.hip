@@ -41,3 +41,4 @@ using namespace nnn;
 #include "nnn_sim.hip"
 #include "nnn_fit.hip"
 #include "nnn_score.hip"
+#include "nnn_gate.hip"
