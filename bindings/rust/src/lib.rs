@@ -43,6 +43,10 @@ pub struct RawScore {
 pub struct RawGate {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct RawMix {
+    _p: [u8; 0],
+}
 
 extern "C" {
     fn nnn_model_from_bytes(bytes: *const u8, len: usize) -> *mut RawModel;
@@ -329,6 +333,41 @@ extern "C" {
     fn nnn_gate_state_bytes(g: *const RawGate) -> usize;
     fn nnn_gate_export_streams(g: *mut RawGate, idx: *const c_int, n: c_int, records: *mut c_void, bytes: usize) -> c_int;
     fn nnn_gate_import_streams(g: *mut RawGate, idx: *const c_int, n: c_int, records: *const c_void, bytes: usize) -> c_int;
+    // include/nnn_mix.h
+    fn nnn_mix_create(n_streams: c_int, device: c_int) -> *mut RawMix;
+    fn nnn_mix_destroy(m: *mut RawMix);
+    fn nnn_mix_set_rooms(m: *mut RawMix, idx: *const c_int, n: c_int, room: *const i32) -> c_int;
+    fn nnn_mix_get_rooms(m: *mut RawMix, idx: *const c_int, n: c_int, room: *mut i32) -> c_int;
+    fn nnn_mix_set_gains(m: *mut RawMix, idx: *const c_int, n: c_int, gain: *const c_float) -> c_int;
+    fn nnn_mix_get_gains(m: *mut RawMix, idx: *const c_int, n: c_int, gain: *mut c_float) -> c_int;
+    fn nnn_mix_reset(m: *mut RawMix, idx: *const c_int, n: c_int) -> c_int;
+    fn nnn_mix_apply_device(
+        m: *mut RawMix,
+        d_in: *const c_float,
+        d_out: *mut c_float,
+        d_talk: *const u8,
+        d_live: *const u8,
+        d_heard: *mut i32,
+        n_frames: c_int,
+        in_stream_stride: usize,
+        in_frame_stride: usize,
+        out_stream_stride: usize,
+        out_frame_stride: usize,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    fn nnn_mix_apply_pcm_device(
+        m: *mut RawMix,
+        d_in: *const c_void,
+        d_out: *mut c_void,
+        d_talk: *const u8,
+        d_live: *const u8,
+        d_heard: *mut i32,
+        n_frames: c_int,
+        in_layout: *const PcmLayout,
+        out_layout: *const PcmLayout,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    fn nnn_mix_apply_host(m: *mut RawMix, input: *const c_float, out: *mut c_float, talk: *const u8, live: *const u8, heard: *mut i32, n_frames: c_int) -> c_int;
 }
 
 /// `struct nnn_gate_params` (include/nnn_gate.h): a stream's gate.  `threshold` and `level` in [0, 1], `grace` 0 ..= 6000 frames,
@@ -1292,6 +1331,121 @@ impl VadGate {
 impl Drop for VadGate {
     fn drop(&mut self) {
         unsafe { nnn_gate_destroy(self.raw) }
+    }
+}
+
+/// The conference mixer behind the gate (include/nnn_mix.h): per stream a room and a gain; every live member of a room receives the sum
+/// of the room's other talkers (mix-minus).  Host buffers are dense `[n_streams][n_frames][480]`, talk flags (the gate's open flags) and
+/// heard counts `[n_frames][n_streams]`, the live mask `[n_streams]`.
+pub struct Mixer {
+    raw: *mut RawMix,
+    n_streams: usize,
+}
+unsafe impl Send for Mixer {}
+
+impl Mixer {
+    pub const MAX_GAIN: f32 = 16.0;
+    pub fn new(n_streams: usize, device: i32) -> Option<Mixer> {
+        let raw = unsafe { nnn_mix_create(n_streams as c_int, device as c_int) };
+        if raw.is_null() {
+            None
+        } else {
+            Some(Mixer { raw, n_streams })
+        }
+    }
+    pub fn num_streams(&self) -> usize {
+        self.n_streams
+    }
+    /// Rooms of the listed streams (`None`: one per stream), -1 = alone; in force from the next call.  Leaves the ramp state alone: mute a
+    /// stream before moving it.
+    pub fn set_rooms(&mut self, idx: Option<&[i32]>, room: &[i32]) -> Result<(), ()> {
+        assert_eq!(room.len(), idx.map_or(self.n_streams, |i| i.len()));
+        let rc = unsafe { nnn_mix_set_rooms(self.raw, idx.map_or(std::ptr::null(), |i| i.as_ptr()), room.len() as c_int, room.as_ptr()) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Gains of the listed streams in `[0, MAX_GAIN]`; a change reaches the audio through a one-frame ramp.
+    pub fn set_gains(&mut self, idx: Option<&[i32]>, gain: &[f32]) -> Result<(), ()> {
+        assert_eq!(gain.len(), idx.map_or(self.n_streams, |i| i.len()));
+        let rc = unsafe { nnn_mix_set_gains(self.raw, idx.map_or(std::ptr::null(), |i| i.as_ptr()), gain.len() as c_int, gain.as_ptr()) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    pub fn rooms(&mut self) -> Vec<i32> {
+        let mut r = vec![0i32; self.n_streams];
+        unsafe { nnn_mix_get_rooms(self.raw, std::ptr::null(), self.n_streams as c_int, r.as_mut_ptr()) };
+        r
+    }
+    pub fn gains(&mut self) -> Vec<f32> {
+        let mut g = vec![0f32; self.n_streams];
+        unsafe { nnn_mix_get_gains(self.raw, std::ptr::null(), self.n_streams as c_int, g.as_mut_ptr()) };
+        g
+    }
+    /// The listed streams (`None`: all) back to "silent so far"; rooms and gains stay.
+    pub fn reset(&mut self, idx: Option<&[i32]>) -> Result<(), ()> {
+        let rc = unsafe { nnn_mix_reset(self.raw, idx.map_or(std::ptr::null(), |i| i.as_ptr()), idx.map_or(0, |i| i.len()) as c_int) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Host memory, never in place; what a stream marked 0 in `live` owns in `out` and `heard` is left as it was.
+    pub fn apply(&mut self, input: &[f32], out: &mut [f32], n_frames: usize, talk: Option<&[u8]>, live: Option<&[u8]>, heard: Option<&mut [i32]>) -> Result<(), ()> {
+        let rows = self.n_streams * n_frames;
+        assert!(input.len() == rows * 480 && out.len() == rows * 480 && talk.map_or(true, |t| t.len() == rows));
+        assert!(live.map_or(true, |l| l.len() == self.n_streams) && heard.as_ref().map_or(true, |h| h.len() == rows));
+        let rc = unsafe {
+            nnn_mix_apply_host(
+                self.raw,
+                input.as_ptr(),
+                out.as_mut_ptr(),
+                talk.map_or(std::ptr::null(), |t| t.as_ptr()),
+                live.map_or(std::ptr::null(), |l| l.as_ptr()),
+                heard.map_or(std::ptr::null_mut(), |h| h.as_mut_ptr()),
+                n_frames as c_int,
+            )
+        };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Raw device pointers, asynchronous on `hip_stream` (null: the mixer's own stream); strides in floats, a pair per side.
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the sizes include/nnn_mix.h states, valid until the call has run; `d_out` must not overlap `d_in`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn apply_device(
+        &mut self,
+        d_in: *const f32,
+        d_out: *mut f32,
+        d_talk: *const u8,
+        d_live: *const u8,
+        d_heard: *mut i32,
+        n_frames: usize,
+        in_strides: (usize, usize),
+        out_strides: (usize, usize),
+        hip_stream: *mut c_void,
+    ) -> Result<(), ()> {
+        let rc = nnn_mix_apply_device(self.raw, d_in, d_out, d_talk, d_live, d_heard, n_frames as c_int, in_strides.0, in_strides.1, out_strides.0, out_strides.1, hip_stream);
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// The packed boundary of `BatchDenoiser::process_pcm_device`, a layout (and format) per side.
+    ///
+    /// # Safety
+    /// As `apply_device`, in elements of each layout's format.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn apply_pcm_device(
+        &mut self,
+        d_in: *const c_void,
+        d_out: *mut c_void,
+        d_talk: *const u8,
+        d_live: *const u8,
+        d_heard: *mut i32,
+        n_frames: usize,
+        in_layout: &PcmLayout,
+        out_layout: &PcmLayout,
+        hip_stream: *mut c_void,
+    ) -> Result<(), ()> {
+        let rc = nnn_mix_apply_pcm_device(self.raw, d_in, d_out, d_talk, d_live, d_heard, n_frames as c_int, in_layout, out_layout, hip_stream);
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+}
+impl Drop for Mixer {
+    fn drop(&mut self) {
+        unsafe { nnn_mix_destroy(self.raw) }
     }
 }
 

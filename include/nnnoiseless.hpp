@@ -28,6 +28,7 @@
 #include "nnn_batch.h"
 #include "nnn_fit.h"
 #include "nnn_gate.h"
+#include "nnn_mix.h"
 #include "nnn_node.h"
 #include "nnn_pack.h"
 #include "nnn_rate.h"
@@ -571,6 +572,72 @@ class VadGate {
     }
     int n_;
     std::shared_ptr<nnn_gate> h_;
+};
+
+// the conference mixer behind the gate (nnn_mix.h): per stream a room and a gain; every live member of a room receives the sum of the room's
+// other talkers (mix-minus); the rule is exact and stated in the header
+class Mixer {
+  public:
+    explicit Mixer(int n_streams, int device = 0) : n_(n_streams), h_(nnn_mix_create(n_streams, device), nnn_mix_destroy)
+    {
+        if (!h_) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    int num_streams() const { return n_; }
+    // rooms (-1 = alone) and gains (0 .. NNN_MIX_MAX_GAIN) of the listed streams (idx empty: one per stream), in force from the next call;
+    // set_rooms leaves the ramp state alone: mute a stream before moving it
+    void set_rooms(const std::vector<int32_t> &room, const std::vector<int> &idx = {})
+    {
+        if (room.size() != (idx.empty() ? (size_t)n_ : idx.size())) throw std::invalid_argument("nnnoiseless: one room per listed stream");
+        check(nnn_mix_set_rooms(h_.get(), idx.empty() ? nullptr : idx.data(), (int)room.size(), room.data()));
+    }
+    void set_gains(const std::vector<float> &gain, const std::vector<int> &idx = {})
+    {
+        if (gain.size() != (idx.empty() ? (size_t)n_ : idx.size())) throw std::invalid_argument("nnnoiseless: one gain per listed stream");
+        check(nnn_mix_set_gains(h_.get(), idx.empty() ? nullptr : idx.data(), (int)gain.size(), gain.data()));
+    }
+    std::vector<int32_t> rooms()
+    {
+        std::vector<int32_t> r((size_t)n_);
+        check(nnn_mix_get_rooms(h_.get(), nullptr, n_, r.data()));
+        return r;
+    }
+    std::vector<float> gains()
+    {
+        std::vector<float> g((size_t)n_);
+        check(nnn_mix_get_gains(h_.get(), nullptr, n_, g.data()));
+        return g;
+    }
+    // idx empty: every stream
+    void reset(const std::vector<int> &idx = {}) { check(nnn_mix_reset(h_.get(), idx.empty() ? nullptr : idx.data(), (int)idx.size())); }
+    // host memory, dense [n_streams][n_frames][480] (out must not be in); talk nullptr or [n_frames][n_streams] (the gate's open flags); live
+    // nullptr or [n_streams]; heard nullptr or [n_frames][n_streams]
+    void apply(const float *in, float *out, int n_frames, const uint8_t *talk = nullptr, const uint8_t *live = nullptr, int32_t *heard = nullptr)
+    {
+        check(nnn_mix_apply_host(h_.get(), in, out, talk, live, heard, n_frames));
+    }
+    // raw device pointers, asynchronous on hip_stream (nullptr = the mixer's own stream); strides in floats, a pair per side; never in place
+    void apply_device(const float *d_in, float *d_out, int n_frames, size_t in_stream_stride, size_t in_frame_stride, size_t out_stream_stride,
+                      size_t out_frame_stride, const uint8_t *d_talk = nullptr, const uint8_t *d_live = nullptr, int32_t *d_heard = nullptr,
+                      void *hip_stream = nullptr)
+    {
+        check(nnn_mix_apply_device(h_.get(), d_in, d_out, d_talk, d_live, d_heard, n_frames, in_stream_stride, in_frame_stride, out_stream_stride,
+                                   out_frame_stride, hip_stream));
+    }
+    // the packed boundary of BatchDenoiser::process_pcm_device, a layout (and format) per side
+    void apply_pcm_device(const void *d_in, void *d_out, int n_frames, const nnn_pcm_layout &in_layout, const nnn_pcm_layout &out_layout,
+                          const uint8_t *d_talk = nullptr, const uint8_t *d_live = nullptr, int32_t *d_heard = nullptr, void *hip_stream = nullptr)
+    {
+        check(nnn_mix_apply_pcm_device(h_.get(), d_in, d_out, d_talk, d_live, d_heard, n_frames, &in_layout, &out_layout, hip_stream));
+    }
+    nnn_mix *raw() { return h_.get(); }
+
+  private:
+    static void check(int rc)
+    {
+        if (rc) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    int n_;
+    std::shared_ptr<nnn_mix> h_;
 };
 
 class DenoiseState {

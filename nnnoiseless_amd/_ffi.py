@@ -74,6 +74,12 @@ GATE_PARAMS_DTYPE = np.dtype([("threshold", "<f4"), ("grace", "<i4"), ("lookback
 # a stream's record (NNN_GATE_STATE_BYTES): the header's fields and the history rows
 GATE_STATE_DTYPE = np.dtype([("magic", "<u4"), ("version", "<u4"), ("size", "<u4"), ("threshold", "<f4"), ("grace", "<i4"), ("lookback", "<i4"),
                              ("level", "<f4"), ("since", "<i4"), ("was_open", "<u4"), ("zero", "<u4", 3), ("history", "<f4", (8, 480))])
+# include/nnn_mix.h (the conference mixer: per-room mix-minus behind the gate; an object beside the batch)
+MIX_SYMBOLS = [
+    "nnn_mix_create", "nnn_mix_destroy", "nnn_mix_set_rooms", "nnn_mix_get_rooms", "nnn_mix_set_gains", "nnn_mix_get_gains", "nnn_mix_reset",
+    "nnn_mix_apply_device", "nnn_mix_apply_pcm_device", "nnn_mix_apply_host",
+]
+MIX_MAX_GAIN, MIX_TILE, MIX_REG_TALKERS = 16, 32, 8
 FIT_PARAMS, FIT_RNN_BYTES, FIT_TILE = 87503, 87521, 4
 FIT_SEL_PARAMS, FIT_SEL_GRAD, FIT_SEL_ADAM_M, FIT_SEL_ADAM_V = 0, 1, 2, 3
 # the fifteen tensors of the parameter vector (NNN_FIT_OFF_*): name -> (offset, shape)
@@ -408,6 +414,20 @@ class Library:
             L.nnn_gate_state_bytes.argtypes = [vp]
             L.nnn_gate_export_streams.argtypes = [vp, ip, i32, vp, sz]
             L.nnn_gate_import_streams.argtypes = [vp, ip, i32, vp, sz]
+        if hasattr(L, "nnn_mix_create"):
+            ip, lp = C.POINTER(i32), C.POINTER(PcmLayout)
+            L.nnn_mix_create.restype = vp
+            L.nnn_mix_create.argtypes = [i32, i32]
+            L.nnn_mix_destroy.restype = None
+            L.nnn_mix_destroy.argtypes = [vp]
+            L.nnn_mix_set_rooms.argtypes = [vp, ip, i32, vp]
+            L.nnn_mix_get_rooms.argtypes = [vp, ip, i32, vp]
+            L.nnn_mix_set_gains.argtypes = [vp, ip, i32, vp]
+            L.nnn_mix_get_gains.argtypes = [vp, ip, i32, vp]
+            L.nnn_mix_reset.argtypes = [vp, ip, i32]
+            L.nnn_mix_apply_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, sz, sz, sz, sz, vp]
+            L.nnn_mix_apply_pcm_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, lp, lp, vp]
+            L.nnn_mix_apply_host.argtypes = [vp, vp, vp, vp, vp, vp, i32]
         L.nnn_last_error.restype = C.c_char_p
         L.rnnoise_create.restype = vp
         L.rnnoise_create.argtypes = [vp]

@@ -42,3 +42,4 @@ using namespace nnn;
 #include "nnn_fit.hip"
 #include "nnn_score.hip"
 #include "nnn_gate.hip"
+#include "nnn_mix.hip"
