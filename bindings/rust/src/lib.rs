@@ -47,6 +47,10 @@ pub struct RawGate {
 pub struct RawMix {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct RawPick {
+    _p: [u8; 0],
+}
 
 extern "C" {
     fn nnn_model_from_bytes(bytes: *const u8, len: usize) -> *mut RawModel;
@@ -368,6 +372,42 @@ extern "C" {
         hip_stream: *mut c_void,
     ) -> c_int;
     fn nnn_mix_apply_host(m: *mut RawMix, input: *const c_float, out: *mut c_float, talk: *const u8, live: *const u8, heard: *mut i32, n_frames: c_int) -> c_int;
+    // include/nnn_pick.h
+    fn nnn_pick_create(n_streams: c_int, device: c_int) -> *mut RawPick;
+    fn nnn_pick_destroy(p: *mut RawPick);
+    fn nnn_pick_set_rooms(p: *mut RawPick, idx: *const c_int, n: c_int, room: *const i32) -> c_int;
+    fn nnn_pick_get_rooms(p: *mut RawPick, idx: *const c_int, n: c_int, room: *mut i32) -> c_int;
+    fn nnn_pick_set_pinned(p: *mut RawPick, idx: *const c_int, n: c_int, pinned: *const u8) -> c_int;
+    fn nnn_pick_get_pinned(p: *mut RawPick, idx: *const c_int, n: c_int, pinned: *mut u8) -> c_int;
+    fn nnn_pick_set_policy(p: *mut RawPick, k: c_int, decay: c_float, stick: c_float) -> c_int;
+    fn nnn_pick_get_policy(p: *mut RawPick, k: *mut c_int, decay: *mut c_float, stick: *mut c_float) -> c_int;
+    fn nnn_pick_reset(p: *mut RawPick, idx: *const c_int, n: c_int) -> c_int;
+    fn nnn_pick_select_device(
+        p: *mut RawPick,
+        d_in: *const c_float,
+        d_open: *const u8,
+        d_live: *const u8,
+        d_talk: *mut u8,
+        d_dominant: *mut i32,
+        d_level: *mut f64,
+        n_frames: c_int,
+        stream_stride: usize,
+        frame_stride: usize,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    fn nnn_pick_select_pcm_device(
+        p: *mut RawPick,
+        d_in: *const c_void,
+        d_open: *const u8,
+        d_live: *const u8,
+        d_talk: *mut u8,
+        d_dominant: *mut i32,
+        d_level: *mut f64,
+        n_frames: c_int,
+        layout: *const PcmLayout,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    fn nnn_pick_select_host(p: *mut RawPick, input: *const c_float, open: *const u8, live: *const u8, talk: *mut u8, dominant: *mut i32, level: *mut f64, n_frames: c_int) -> c_int;
 }
 
 /// `struct nnn_gate_params` (include/nnn_gate.h): a stream's gate.  `threshold` and `level` in [0, 1], `grace` 0 ..= 6000 frames,
@@ -1446,6 +1486,134 @@ impl Mixer {
 impl Drop for Mixer {
     fn drop(&mut self) {
         unsafe { nnn_mix_destroy(self.raw) }
+    }
+}
+
+/// The talker picker between the gate and the mixer (include/nnn_pick.h): per stream a room and a pin, per object `k`, `decay` and
+/// `stick`; of every room's open gates the `k` loudest talk, and an incumbent keeps its place until a challenger is `stick` times louder.
+/// Host audio is dense `[n_streams][n_frames][480]`; open flags (the gate's), talk flags (what `Mixer::apply` takes), dominant indices and
+/// levels are `[n_frames][n_streams]`, the live mask `[n_streams]`.
+pub struct Picker {
+    raw: *mut RawPick,
+    n_streams: usize,
+}
+unsafe impl Send for Picker {}
+
+impl Picker {
+    pub const MAX_K: i32 = 8;
+    pub const MAX_STICK: f32 = 16.0;
+    pub fn new(n_streams: usize, device: i32) -> Option<Picker> {
+        let raw = unsafe { nnn_pick_create(n_streams as c_int, device as c_int) };
+        if raw.is_null() {
+            None
+        } else {
+            Some(Picker { raw, n_streams })
+        }
+    }
+    pub fn num_streams(&self) -> usize {
+        self.n_streams
+    }
+    /// Rooms of the listed streams (`None`: one per stream), -1 = alone: the mixer's labels; in force from the next call.
+    pub fn set_rooms(&mut self, idx: Option<&[i32]>, room: &[i32]) -> Result<(), ()> {
+        assert_eq!(room.len(), idx.map_or(self.n_streams, |i| i.len()));
+        let rc = unsafe { nnn_pick_set_rooms(self.raw, idx.map_or(std::ptr::null(), |i| i.as_ptr()), room.len() as c_int, room.as_ptr()) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Pins of the listed streams, each 0 or 1: a pinned stream with an open gate ranks ahead of every unpinned one.
+    pub fn set_pinned(&mut self, idx: Option<&[i32]>, pinned: &[u8]) -> Result<(), ()> {
+        assert_eq!(pinned.len(), idx.map_or(self.n_streams, |i| i.len()));
+        let rc = unsafe { nnn_pick_set_pinned(self.raw, idx.map_or(std::ptr::null(), |i| i.as_ptr()), pinned.len() as c_int, pinned.as_ptr()) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// `k` in `1 ..= MAX_K`, `decay` in `[0, 1]`, `stick` in `[1, MAX_STICK]`.
+    pub fn set_policy(&mut self, k: i32, decay: f32, stick: f32) -> Result<(), ()> {
+        let rc = unsafe { nnn_pick_set_policy(self.raw, k as c_int, decay, stick) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    pub fn rooms(&mut self) -> Vec<i32> {
+        let mut r = vec![0i32; self.n_streams];
+        unsafe { nnn_pick_get_rooms(self.raw, std::ptr::null(), self.n_streams as c_int, r.as_mut_ptr()) };
+        r
+    }
+    pub fn pinned(&mut self) -> Vec<u8> {
+        let mut p = vec![0u8; self.n_streams];
+        unsafe { nnn_pick_get_pinned(self.raw, std::ptr::null(), self.n_streams as c_int, p.as_mut_ptr()) };
+        p
+    }
+    pub fn policy(&mut self) -> (i32, f32, f32) {
+        let (mut k, mut decay, mut stick) = (0 as c_int, 0f32, 0f32);
+        unsafe { nnn_pick_get_policy(self.raw, &mut k, &mut decay, &mut stick) };
+        (k as i32, decay, stick)
+    }
+    /// The listed streams (`None`: all) back to "silent and not selected so far"; rooms, pins and policy stay.
+    pub fn reset(&mut self, idx: Option<&[i32]>) -> Result<(), ()> {
+        let rc = unsafe { nnn_pick_reset(self.raw, idx.map_or(std::ptr::null(), |i| i.as_ptr()), idx.map_or(0, |i| i.len()) as c_int) };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Host memory; what a stream marked 0 in `live` owns in `talk`, `dominant` and `level` is left as it was.
+    #[allow(clippy::too_many_arguments)]
+    pub fn select(&mut self, input: &[f32], talk: &mut [u8], n_frames: usize, open: Option<&[u8]>, live: Option<&[u8]>, dominant: Option<&mut [i32]>, level: Option<&mut [f64]>) -> Result<(), ()> {
+        let rows = self.n_streams * n_frames;
+        assert!(input.len() == rows * 480 && talk.len() == rows && open.map_or(true, |o| o.len() == rows));
+        assert!(live.map_or(true, |l| l.len() == self.n_streams) && dominant.as_ref().map_or(true, |d| d.len() == rows) && level.as_ref().map_or(true, |l| l.len() == rows));
+        let rc = unsafe {
+            nnn_pick_select_host(
+                self.raw,
+                input.as_ptr(),
+                open.map_or(std::ptr::null(), |o| o.as_ptr()),
+                live.map_or(std::ptr::null(), |l| l.as_ptr()),
+                talk.as_mut_ptr(),
+                dominant.map_or(std::ptr::null_mut(), |d| d.as_mut_ptr()),
+                level.map_or(std::ptr::null_mut(), |l| l.as_mut_ptr()),
+                n_frames as c_int,
+            )
+        };
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// Raw device pointers, asynchronous on `hip_stream` (null: the picker's own stream); strides in floats; `d_talk` may be `d_open` itself.
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the sizes include/nnn_pick.h states, valid until the call has run.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn select_device(
+        &mut self,
+        d_in: *const f32,
+        d_open: *const u8,
+        d_live: *const u8,
+        d_talk: *mut u8,
+        d_dominant: *mut i32,
+        d_level: *mut f64,
+        n_frames: usize,
+        strides: (usize, usize),
+        hip_stream: *mut c_void,
+    ) -> Result<(), ()> {
+        let rc = nnn_pick_select_device(self.raw, d_in, d_open, d_live, d_talk, d_dominant, d_level, n_frames as c_int, strides.0, strides.1, hip_stream);
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+    /// The packed boundary of `BatchDenoiser::process_pcm_device`.
+    ///
+    /// # Safety
+    /// As `select_device`, in elements of the layout's format.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn select_pcm_device(
+        &mut self,
+        d_in: *const c_void,
+        d_open: *const u8,
+        d_live: *const u8,
+        d_talk: *mut u8,
+        d_dominant: *mut i32,
+        d_level: *mut f64,
+        n_frames: usize,
+        layout: &PcmLayout,
+        hip_stream: *mut c_void,
+    ) -> Result<(), ()> {
+        let rc = nnn_pick_select_pcm_device(self.raw, d_in, d_open, d_live, d_talk, d_dominant, d_level, n_frames as c_int, layout, hip_stream);
+        if rc == 0 { Ok(()) } else { Err(()) }
+    }
+}
+impl Drop for Picker {
+    fn drop(&mut self) {
+        unsafe { nnn_pick_destroy(self.raw) }
     }
 }
 

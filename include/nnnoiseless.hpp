@@ -29,6 +29,7 @@
 #include "nnn_fit.h"
 #include "nnn_gate.h"
 #include "nnn_mix.h"
+#include "nnn_pick.h"
 #include "nnn_node.h"
 #include "nnn_pack.h"
 #include "nnn_rate.h"
@@ -638,6 +639,74 @@ class Mixer {
     }
     int n_;
     std::shared_ptr<nnn_mix> h_;
+};
+
+// the talker picker between the gate and the mixer (nnn_pick.h): per stream a room and a pin, per object k, decay and stick; of every
+// room's open gates the k loudest talk, an incumbent keeps its place until a challenger is stick times louder; the rule is exact and
+// stated in the header
+class Picker {
+  public:
+    explicit Picker(int n_streams, int device = 0) : n_(n_streams), h_(nnn_pick_create(n_streams, device), nnn_pick_destroy)
+    {
+        if (!h_) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    int num_streams() const { return n_; }
+    // rooms (-1 = alone; the mixer's labels) and pins (0 or 1) of the listed streams (idx empty: one per stream), in force from the next call
+    void set_rooms(const std::vector<int32_t> &room, const std::vector<int> &idx = {})
+    {
+        if (room.size() != (idx.empty() ? (size_t)n_ : idx.size())) throw std::invalid_argument("nnnoiseless: one room per listed stream");
+        check(nnn_pick_set_rooms(h_.get(), idx.empty() ? nullptr : idx.data(), (int)room.size(), room.data()));
+    }
+    void set_pinned(const std::vector<uint8_t> &pinned, const std::vector<int> &idx = {})
+    {
+        if (pinned.size() != (idx.empty() ? (size_t)n_ : idx.size())) throw std::invalid_argument("nnnoiseless: one pin per listed stream");
+        check(nnn_pick_set_pinned(h_.get(), idx.empty() ? nullptr : idx.data(), (int)pinned.size(), pinned.data()));
+    }
+    // k in 1 .. NNN_PICK_MAX_K, decay in [0, 1], stick in [1, NNN_PICK_MAX_STICK]
+    void set_policy(int k, float decay, float stick) { check(nnn_pick_set_policy(h_.get(), k, decay, stick)); }
+    std::vector<int32_t> rooms()
+    {
+        std::vector<int32_t> r((size_t)n_);
+        check(nnn_pick_get_rooms(h_.get(), nullptr, n_, r.data()));
+        return r;
+    }
+    std::vector<uint8_t> pinned()
+    {
+        std::vector<uint8_t> p((size_t)n_);
+        check(nnn_pick_get_pinned(h_.get(), nullptr, n_, p.data()));
+        return p;
+    }
+    void policy(int &k, float &decay, float &stick) { check(nnn_pick_get_policy(h_.get(), &k, &decay, &stick)); }
+    // idx empty: every stream
+    void reset(const std::vector<int> &idx = {}) { check(nnn_pick_reset(h_.get(), idx.empty() ? nullptr : idx.data(), (int)idx.size())); }
+    // host memory: in dense [n_streams][n_frames][480]; talk [n_frames][n_streams] (what Mixer::apply takes as talk); open nullptr or
+    // [n_frames][n_streams] (the gate's open flags); live nullptr or [n_streams]; dominant and level nullptr or [n_frames][n_streams]
+    void select(const float *in, uint8_t *talk, int n_frames, const uint8_t *open = nullptr, const uint8_t *live = nullptr, int32_t *dominant = nullptr,
+                double *level = nullptr)
+    {
+        check(nnn_pick_select_host(h_.get(), in, open, live, talk, dominant, level, n_frames));
+    }
+    // raw device pointers, asynchronous on hip_stream (nullptr = the picker's own stream); strides in floats; d_talk may be d_open itself
+    void select_device(const float *d_in, uint8_t *d_talk, int n_frames, size_t stream_stride, size_t frame_stride, const uint8_t *d_open = nullptr,
+                       const uint8_t *d_live = nullptr, int32_t *d_dominant = nullptr, double *d_level = nullptr, void *hip_stream = nullptr)
+    {
+        check(nnn_pick_select_device(h_.get(), d_in, d_open, d_live, d_talk, d_dominant, d_level, n_frames, stream_stride, frame_stride, hip_stream));
+    }
+    // the packed boundary of BatchDenoiser::process_pcm_device
+    void select_pcm_device(const void *d_in, uint8_t *d_talk, int n_frames, const nnn_pcm_layout &layout, const uint8_t *d_open = nullptr,
+                           const uint8_t *d_live = nullptr, int32_t *d_dominant = nullptr, double *d_level = nullptr, void *hip_stream = nullptr)
+    {
+        check(nnn_pick_select_pcm_device(h_.get(), d_in, d_open, d_live, d_talk, d_dominant, d_level, n_frames, &layout, hip_stream));
+    }
+    nnn_pick *raw() { return h_.get(); }
+
+  private:
+    static void check(int rc)
+    {
+        if (rc) throw std::runtime_error(std::string("nnnoiseless: ") + nnn_last_error());
+    }
+    int n_;
+    std::shared_ptr<nnn_pick> h_;
 };
 
 class DenoiseState {

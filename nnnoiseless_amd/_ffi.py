@@ -80,6 +80,12 @@ MIX_SYMBOLS = [
     "nnn_mix_apply_device", "nnn_mix_apply_pcm_device", "nnn_mix_apply_host",
 ]
 MIX_MAX_GAIN, MIX_TILE, MIX_REG_TALKERS = 16, 32, 8
+# include/nnn_pick.h (the talker picker: the k loudest open gates of a room, between the gate and the mixer; an object beside the batch)
+PICK_SYMBOLS = [
+    "nnn_pick_create", "nnn_pick_destroy", "nnn_pick_set_rooms", "nnn_pick_get_rooms", "nnn_pick_set_pinned", "nnn_pick_get_pinned",
+    "nnn_pick_set_policy", "nnn_pick_get_policy", "nnn_pick_reset", "nnn_pick_select_device", "nnn_pick_select_pcm_device", "nnn_pick_select_host",
+]
+PICK_MAX_K, PICK_MAX_STICK, PICK_SEG_ROOM, PICK_WAVE_ROOM = 8, 16, 8, 64
 FIT_PARAMS, FIT_RNN_BYTES, FIT_TILE = 87503, 87521, 4
 FIT_SEL_PARAMS, FIT_SEL_GRAD, FIT_SEL_ADAM_M, FIT_SEL_ADAM_V = 0, 1, 2, 3
 # the fifteen tensors of the parameter vector (NNN_FIT_OFF_*): name -> (offset, shape)
@@ -428,6 +434,22 @@ class Library:
             L.nnn_mix_apply_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, sz, sz, sz, sz, vp]
             L.nnn_mix_apply_pcm_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, lp, lp, vp]
             L.nnn_mix_apply_host.argtypes = [vp, vp, vp, vp, vp, vp, i32]
+        if hasattr(L, "nnn_pick_create"):
+            ip, lp, fp = C.POINTER(i32), C.POINTER(PcmLayout), C.POINTER(C.c_float)
+            L.nnn_pick_create.restype = vp
+            L.nnn_pick_create.argtypes = [i32, i32]
+            L.nnn_pick_destroy.restype = None
+            L.nnn_pick_destroy.argtypes = [vp]
+            L.nnn_pick_set_rooms.argtypes = [vp, ip, i32, vp]
+            L.nnn_pick_get_rooms.argtypes = [vp, ip, i32, vp]
+            L.nnn_pick_set_pinned.argtypes = [vp, ip, i32, vp]
+            L.nnn_pick_get_pinned.argtypes = [vp, ip, i32, vp]
+            L.nnn_pick_set_policy.argtypes = [vp, i32, C.c_float, C.c_float]
+            L.nnn_pick_get_policy.argtypes = [vp, ip, fp, fp]
+            L.nnn_pick_reset.argtypes = [vp, ip, i32]
+            L.nnn_pick_select_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, sz, sz, vp]
+            L.nnn_pick_select_pcm_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, lp, vp]
+            L.nnn_pick_select_host.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32]
         L.nnn_last_error.restype = C.c_char_p
         L.rnnoise_create.restype = vp
         L.rnnoise_create.argtypes = [vp]

@@ -43,3 +43,4 @@ using namespace nnn;
 #include "nnn_score.hip"
 #include "nnn_gate.hip"
 #include "nnn_mix.hip"
+#include "nnn_pick.hip"
